@@ -4,13 +4,20 @@ x T=1000 x 60-dim mgc static+delta+delta-delta = 180 columns, float64, per-frame
 variances, standard 3 windows), weak-scaled over N GPUs (one process per GPU,
 independent shards, no data-path collective).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script launches its own N ranks (it
 re-executes itself under torch.distributed.run on 127.0.0.1) and fails loudly if the node has
 fewer than N GPUs.  A "step" is one pass of the hot path (one mlpg_hip_forward launch through the
 C ABI) over the rank's resident batch.  Rank 0 prints ONE JSON line.
+
+A plain run does what the headline figure needs: it generates the inputs, runs the preconditioning
+leg and the W warm-up steps, times exactly K steps, checks their status array, writes the outputs
+of the last timed step if --dump-outputs is given, and prints the line.  --full adds everything
+else: the in-run copy-rate peak, the cold protocol, the steady and repeat regions, the oracle
+parity checks, the live PMC traffic pass, `secondary`, `cpu_baseline` and (N > 1) the in-run
+single-GPU leg.
 """
 import argparse
 import json
@@ -25,6 +32,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_LIMIT = 48 << 20          # bytes of trajectories --dump-outputs writes at most
 WINDOWS = [
     (0, 0, np.array([1.0])),
     (1, 1, np.array([-0.5, 0.0, 0.5])),
@@ -56,7 +64,38 @@ def parse():
                          "copy-rate measurement in front of them does not do it -- and a batch job runs thousands of steps; 0: none")
     ap.add_argument("--regions", type=int, default=9,
                     help="extra timed regions of --steps launches after the official one; their median is reported beside it")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (copy-rate peak, cold protocol, steady and "
+                         "repeat regions, oracle parity, live PMC traffic, `secondary`, cpu_baseline, N > 1: the single-GPU leg); "
+                         "the --no-* options and --regions select among these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64; rank 0's "
+                         "shard; a fixed, seeded sample of whole utterances where the batch's output exceeds %d MiB)" % (DUMP_LIMIT >> 20))
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.dry_run_cpu:
+        ap.error("--dump-outputs needs a GPU run (a --dry-run-cpu step computes nothing)")
+    return args
+
+
+def dump_outputs(d, out, status):
+    """What the timed path returned in its last step: `mlpg_out` (the trajectories, (k, T, static_dim) float64, utterances
+    `mlpg_out_utterances` of the batch) and `status` (one int32 per system, as float64).  The inputs are seeded, so two
+    builds run with the same arguments can be compared array for array."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    B = out.shape[0]
+    per = out[0].numel() * 8                    # bytes of one utterance's trajectories, written as float64
+    k = max(1, min(B, DUMP_LIMIT // max(per, 1)))
+    idx = np.arange(B) if k == B else np.sort(np.random.RandomState(0).choice(B, k, replace=False))
+    y = out.index_select(0, torch.from_numpy(idx).to(out.device)).to(torch.float64).cpu().numpy()
+    if y.nbytes > DUMP_LIMIT:          # one utterance alone is larger than the limit: its leading frames
+        y = y[:, :max(1, DUMP_LIMIT // (y.shape[2] * 8))]
+    np.save(os.path.join(d, "mlpg_out.npy"), y)
+    np.save(os.path.join(d, "mlpg_out_utterances.npy"), idx.astype(np.float64))
+    if status is not None:
+        np.save(os.path.join(d, "status.npy"), status.cpu().numpy().astype(np.float64))
 
 
 _REF_WORKER = r"""
@@ -183,10 +222,9 @@ def live_traffic(B, T, sd, algo, timeout_s=90.0):
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="bench_pmc_", dir="/tmp")
         try:
-            cmd = [prof, "--kernel-trace", "--pmc", counter, "-d", d, "-o", "run", "--", sys.executable,
-                   os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-secondary", "--no-traffic", "--regions", "0",
-                   "--steps", "5", "--warmup", "1", "--algo", str(algo), "--batch", str(B), "--frames", str(T),
-                   "--static-dim", str(sd)]
+            cmd = [prof, "--kernel-trace", "--pmc", counter, "-d", d, "-o", "run", "--", sys.executable,   # a plain run (no --full)
+                   os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1", "--algo", str(algo), "--batch", str(B),
+                   "--frames", str(T), "--static-dim", str(sd)]
             env = dict(os.environ, TMPDIR="/tmp")
             for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
                 env.pop(k, None)
@@ -385,8 +423,9 @@ def main():
     # measured peak beside the nominal 8 TB/s: best of 16 groups of 50 copies.  Taken BEFORE the warm-up steps (about
     # 0.15 s of copies; the clocks of an idle MI355X settle over roughly 0.1 s of work -- see `repeat_regions`): the timed
     # region then starts on a GPU that has been busy for a while, as it is in any batch job, not 3 launches after idle.
+    # --full only: the headline figure does not need it (the preconditioning leg below settles the clocks).
     copy_gbs = None
-    if rank == 0 and not dry:
+    if rank == 0 and not dry and args.full:
         nb = 512 << 20
         src = torch.empty(nb // 4, dtype=torch.float32, device=dev).normal_()
         dst = torch.empty_like(src)
@@ -410,9 +449,9 @@ def main():
 
     # The driver's protocol TO THE LETTER first -- W untimed steps, then exactly K timed ones, nothing in front -- reported as
     # `cold_protocol` / roofline.kernel_ms_cold: what a short job sees, on clocks that are still ramping (profiles/r05_notes.md
-    # section 18).  `value` is the same region taken again behind the preconditioning leg below, on settled clocks.
+    # section 18).  `value` is the same region taken again behind the preconditioning leg below, on settled clocks.  --full only.
     cold = None
-    if not dry:
+    if not dry and args.full:
         for _ in range(args.warmup):
             step()
         sync()
@@ -429,6 +468,7 @@ def main():
     # The device's clocks settle over tens of milliseconds of this kernel (`repeat_regions` below showed regions of 20 steps at
     # 0.2093-0.2116 ms once a few hundred steps had run, against 0.221-0.237 ms for the same region 5 steps after the copy
     # measurement): a leg of the same steps in front of the official warm-up, event-timed and reported (kernel_ms_steady).
+    # Plain runs too: `value` is the settled-clock figure.
     steady_ms = None
     if not dry and args.precondition > 0:
         timed(args.precondition - args.precondition // 2)
@@ -438,9 +478,9 @@ def main():
         out, status = step()
     sync()
 
-    # in-run single-GPU leg (N > 1 only): rank 0 alone, the others idle, same kernel and batch
+    # in-run single-GPU leg (N > 1 and --full only): rank 0 alone, the others idle, same kernel and batch
     solo = None
-    if world > 1:
+    if world > 1 and args.full:
         barrier()
         if rank == 0:
             el, _, _, _ = timed(args.steps)
@@ -451,6 +491,8 @@ def main():
     sync()
     elapsed, kern_ms, out, status = timed(args.steps)
     barrier()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, status)
 
     if not dry:
         if not args.no_check:
@@ -512,12 +554,12 @@ def main():
         gather_ms = (time.perf_counter() - g0) * 1e3
 
     # a longer steady-state leg (informational): the driver's --steps 20 is a ~4 ms region
-    if steady_ms is None and rank == 0 and not dry:
+    if steady_ms is None and rank == 0 and not dry and args.full:
         _, steady_ms, _, _ = timed(max(200, args.steps))
 
     # the official region is short at the driver's --steps (a few ms): repeat it and report the spread beside it
     regions = None
-    if not dry and args.regions > 0:
+    if not dry and args.full and args.regions > 0:
         rs = []
         for _ in range(args.regions):
             barrier()
@@ -530,12 +572,12 @@ def main():
 
     # the other BASELINE configs and kernel variants (after the metric; never part of `value`)
     secondary = None
-    if not args.no_secondary and (not dry or world > 1):
+    if args.full and not args.no_secondary and (not dry or world > 1):
         secondary = collect_secondary(rank, world, local_rank, copy_gbs, dry=dry)
 
     if rank == 0:
         err = err_tight = None
-        if not dry:
+        if not dry and args.full:
             # parity spot checks outside the timed region (oracle = checker only): the first 4 utterances of the timed batch
             #  and the last one, then the same batch with the dynamic variances 100 x / 1000 x tighter -- the strip
             # kernel's other level-3 rungs, which the timed data never takes -- utterances 0 and B - 1
@@ -559,8 +601,8 @@ def main():
                 assert err_tight < 1e-9, err_tight
 
         # HBM traffic of the dominant kernel: measured now (N = 1), else the committed PMC pass of this command
-        traffic, traffic_note = None, "not measured"
-        if not dry:
+        traffic, traffic_note = None, "not measured" if args.full else "not measured (bench.py --full measures it)"
+        if not dry and args.full:
             why = "skipped (--no-traffic)" if args.no_traffic else "N > 1"
             if world == 1 and not args.no_traffic:
                 traffic, why = live_traffic(B, T, sd, args.algo)
@@ -590,6 +632,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f64",
             "data": "synthetic",
+            "full": args.full,
             "config": {
                 "workload": "BASELINE configs[1]: %d utterances/GPU x T=%d x %d-dim mgc static+delta+delta-delta "
                             "(%d columns), float64, per-frame variances, std 3 windows; mlpg_hip_forward via C ABI"
@@ -637,7 +680,7 @@ def main():
             res["repeat_regions"] = regions
         if secondary is not None:
             res["secondary"] = secondary
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if world == 1 and args.full and not args.no_cpu_baseline and not dry:
             res["cpu_baseline"] = cpu_baseline(T, D, args.cpu_seconds)
         print(json.dumps(res), flush=True)
     if use_dist:

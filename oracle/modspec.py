@@ -3,7 +3,7 @@ algorithm: the reference calls it directly).  Imported by tests/ only; never by 
 
 Follows /root/reference/nnmnkwii/preprocessing/modspec.py (modspec :6-53, inv_modspec :62-100, modspec_smoothing
 :103-167) and the analytic gradient of /root/reference/nnmnkwii/autograd/_impl/modspec.py:30-60.  Pinned against the
-goldens the reference itself produced (tests/golden/mlpg_golden.npz: modspec/*, modspec_grad/*) by
+goldens the reference itself produced (tests/golden/mlpg_golden_part*.npz: modspec/*, modspec_grad/*) by
 tests/test_oracle_cpu.py::test_modspec_oracle_matches_reference_goldens; the GPU tests then use it for DFT lengths the
 goldens do not hold (non powers of two, n > 4096).
 """

@@ -15,8 +15,8 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def golden():
-    import numpy as np
-    return np.load(os.path.join(ROOT, "tests", "golden", "mlpg_golden.npz"))
+    import golden_io
+    return golden_io.load("mlpg_golden")
 
 
 @pytest.fixture(scope="session", autouse=True)

@@ -210,9 +210,9 @@ def main():
     out["err/negvar-msg"] = np.array(msg)
     out["err/negvar-v"] = v
 
-    path = os.path.join(HERE, "mlpg_golden.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, len(out), "arrays,", os.path.getsize(path) // 1024, "KiB")
+    import golden_io
+    paths = golden_io.save("mlpg_golden", out)
+    print("wrote", paths, len(out), "arrays,", sum(os.path.getsize(p) for p in paths) // 1024, "KiB")
 
 
 if __name__ == "__main__":

@@ -1,4 +1,4 @@
-"""Round-2 goldens, again from the REFERENCE ITSELF (tests/golden/mlpg_golden2.npz, align_golden2.npz).
+"""Round-2 goldens, again from the REFERENCE ITSELF (tests/golden/mlpg_golden2.npz, align_golden2_part*.npz).
 
 Run in the build container only (needs /root/reference):
 
@@ -84,8 +84,9 @@ def main():
     Xa, Ya = DTWAligner(dist=melcd).transform((X, Y))
     out["dtw-melcd/c4/Xa"] = Xa
     out["dtw-melcd/c4/Ya"] = Ya
-    np.savez_compressed(os.path.join(HERE, "align_golden2.npz"), **out)
-    print("wrote align_golden2.npz", {k: v.shape for k, v in out.items()})
+    import golden_io
+    golden_io.save("align_golden2", out)
+    print("wrote align_golden2_part*.npz", {k: v.shape for k, v in out.items()})
 
 
 if __name__ == "__main__":

@@ -167,7 +167,7 @@ def test_bench_under_the_drivers_launcher_with_the_rccl_backend_at_world_size_on
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
                         "--batch", "32", "--frames", "300", "--precondition", "0", "--regions", "0", "--no-cpu-baseline", "--no-secondary",
-                        "--no-traffic", "--gather"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                        "--no-traffic", "--gather", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert res["n_gpus"] == 1 and res["value"] > 0 and res["allgather_ms"] is not None and res["parity_rel_err_vs_oracle"] < 1e-9

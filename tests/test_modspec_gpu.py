@@ -16,7 +16,8 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def golden():
-    return np.load(os.path.join(HERE, "golden", "mlpg_golden.npz"))
+    import golden_io
+    return golden_io.load("mlpg_golden")
 
 
 def _close(a, b, rel):

@@ -182,9 +182,9 @@ def test_oracle_vs_compiled_reference():
 def test_modspec_oracle_matches_reference_goldens():
     """oracle/modspec.py (numpy's FFT, as the reference) against every modulation-spectrum golden the reference
     produced (make_golden.py): spectrum, phase, inverse, smoothing in both domains and norms, analytic gradient."""
-    import os
+    import golden_io
     from oracle import modspec as OM
-    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mlpg_golden.npz"))
+    g = golden_io.load("mlpg_golden")
     seen = 0
     for key in [k for k in g.files if k.startswith("modspec/T") and k.endswith("/x")]:
         case = key[:-2]

@@ -9,7 +9,7 @@
   R @ means of the reference's definition evaluated in float64 on the host (R = the oracle's restatement of
   unit_variance_mlpg_matrix, itself checked against rows produced by the reference);
 * BASELINE config 4 sized DTW pairs through DTWAligner against the reference's unmodified alignment.py run with its
-  own dist = norm(x - y) (align_golden2.npz).
+  own dist = norm(x - y) (align_golden2_part*.npz).
 """
 import os
 import sys
@@ -20,6 +20,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 from cases import WINDOW_SETS, c4_pairs, rand_case  # noqa: E402
+import golden_io  # noqa: E402
 from oracle import mlpg as O  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -129,7 +130,7 @@ def test_config3_size_unit_variance_autograd(golden2):
 
 def test_config4_size_dtw_aligner_vs_reference_alignment():
     from nnmnkwii_amd.preprocessing.alignment import DTWAligner
-    g = np.load(os.path.join(HERE, "golden", "align_golden2.npz"))
+    g = golden_io.load("align_golden2")
     X, Y = c4_pairs(6)
     Xa, Ya = DTWAligner().transform((X, Y))
     assert Xa.shape == g["dtw4/Xa"].shape and Ya.shape == g["dtw4/Ya"].shape
@@ -144,7 +145,7 @@ def test_dtw_aligner_custom_dist_melcd_vs_reference(name):
     from cases import align_batch
     from nnmnkwii_amd.metrics import melcd
     from nnmnkwii_amd.preprocessing.alignment import DTWAligner
-    g = np.load(os.path.join(HERE, "golden", "align_golden2.npz"))
+    g = golden_io.load("align_golden2")
     X, Y = c4_pairs(2, seed=99) if name == "c4" else align_batch(name)
     Xa, Ya = DTWAligner(dist=melcd).transform((X, Y))
     np.testing.assert_array_equal(Xa, g["dtw-melcd/%s/Xa" % name])

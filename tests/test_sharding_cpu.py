@@ -127,7 +127,7 @@ def test_bench_self_launches_its_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--dry-run-cpu"], capture_output=True, text=True, timeout=300, env=env)
+                        "--dry-run-cpu", "--full"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     res = json.loads(line)
@@ -157,7 +157,7 @@ def test_bench_at_world_size_8_under_the_drivers_launcher():
     env["OMP_NUM_THREADS"] = "1"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
-                        "--dry-run-cpu"], capture_output=True, text=True, timeout=600, env=env)
+                        "--dry-run-cpu", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1                                   # rank 0 alone prints

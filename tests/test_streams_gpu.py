@@ -18,7 +18,8 @@ STD3 = WINDOW_SETS["std3"]
 
 @pytest.fixture(scope="module")
 def golden():
-    return np.load(os.path.join(HERE, "golden", "mlpg_golden.npz"))
+    import golden_io
+    return golden_io.load("mlpg_golden")
 
 
 def test_merlin_example_utterance_matches_reference(golden):
