@@ -1,0 +1,234 @@
+"""The stream plan of mlpg_hip_forward_streams (nnmnkwii_amd/csrc/capi.hip) restated in plain Python, with no GPU: which
+streams share the merged launch and in which lane order, where the launch is trimmed (`cap`), which stream is cut into a head
+and a piece, and which streams run on their own.  For forced families the launch counters the call moves are predicted
+exactly; under AUTO only the merged launch and the number of launches are.
+
+A stream is a dict with in_col, out_col, static_dim, num_windows, win_first (mlpg_hip_stream_t); the window tables are the
+packed (l[], u[], coeff[]) of include/mlpg_hip.h.  The support and preference predicates below restate csrc/mlpg_*.hip for
+the problems the stream tests build (every row inside the 2 GB buffer window)."""
+import collections
+
+import numpy as np
+
+F32, F64 = 0, 1
+VAR_FRAME, VAR_GLOBAL, VAR_UNIT = 0, 1, 2
+AUTO, GENERIC, WAVE, STRIP, CONST, CHUNK, FIR = 0, 1, 2, 3, 5, 6, 7
+ALGO_NAME = {GENERIC: "GENERIC", WAVE: "WAVE", STRIP: "STRIP", CONST: "CONST", CHUNK: "CHUNK", FIR: "FIR"}
+# launch counter kinds (mlpg_hip_launch_count) of the forward families
+K_GENERIC, K_WAVE, K_STRIP, K_STRIP_MULTI, K_CONST, K_CHUNK, K_FIR, K_CONST_MULTI, K_STRIP_TR = 0, 1, 2, 3, 4, 6, 7, 8, 9
+FORWARD_KINDS = (0, 1, 2, 3, 4, 6, 7, 8, 9)
+STRIP_FRAMES, MAX_STRIPS = 64, 256
+
+
+class Win(object):
+    """The packed window set of one stream (capi.hip pack_windows): nw, l, u, mw (max extent), q (max l + u), c0."""
+
+    def __init__(self, wl, wu, wc, first, nw):
+        off = sum(int(wl[w]) + int(wu[w]) + 1 for w in range(first))
+        self.nw = nw
+        self.l = [int(x) for x in wl[first:first + nw]]
+        self.u = [int(x) for x in wu[first:first + nw]]
+        self.mw = max([max(a, b) for a, b in zip(self.l, self.u)] + [0])
+        self.ext1 = all(a <= 1 and b <= 1 for a, b in zip(self.l, self.u))
+        self.c0 = float(wc[off]) if nw else 0.0
+
+
+# ---- support / preference predicates (csrc/mlpg_strip.hip, mlpg_wave.hip, mlpg_const.hip, mlpg_chunk.hip, mlpg_fir.hip)
+
+def strip_supported(T, ws):
+    return T >= 1 and (T + STRIP_FRAMES - 1) // STRIP_FRAMES <= MAX_STRIPS and ws.ext1
+
+
+def strip_preferred(B, T, sd, var_mode, ws):
+    if not strip_supported(T, ws):
+        return False
+    if sd >= 16 and T > 1024:
+        return True
+    ndg = (sd + 63) // 64
+    dgw = (sd + ndg - 1) // ndg
+    return dgw >= 48 and var_mode == VAR_FRAME and B * ndg * ((T + 63) // 64) >= 512
+
+
+def strip_tr_supported(B, T, sd, ld, ws):
+    if ws.nw != 3 or sd < 1 or sd > 32 or B < 2 or not strip_supported(T, ws):
+        return False
+    return (64 // sd) * T * ld * 8.0 < 2147483647.0
+
+
+def strip_tr_preferred(B, T, sd, ld, dtype, ws):
+    if not strip_tr_supported(B, T, sd, ld, ws):
+        return False
+    u = 64 // sd
+    items = ((B + u - 1) // u) * ((T + 63) // 64)
+    if B < u:
+        return False
+    if T > 1024:
+        return items >= 64
+    return items >= (512 if dtype == F32 else 256)
+
+
+def wave_supported(T, ws):
+    return 1 <= T <= 2048 and ws.ext1
+
+
+def const_supported(B, T, sd, var_mode, ws, piece=False):
+    return (var_mode in (VAR_GLOBAL, VAR_UNIT) and ws.nw in (2, 3) and ws.mw == 1 and ws.ext1 and not piece
+            and T >= 1 and sd >= 1 and B >= 1)
+
+
+def const_preferred(B, T, sd, var_mode, ws):
+    if not const_supported(B, T, sd, var_mode, ws):
+        return False
+    ndg = (sd + 63) // 64
+    return (sd + ndg - 1) // ndg >= 32 and B * ndg >= 192
+
+
+def chunk_supported(ws, piece=False):
+    return 1 <= ws.nw <= 3 and 1 <= ws.mw <= 2 and not piece
+
+
+def chunk_preferred(B, T, sd, ws):
+    return chunk_supported(ws) and ws.mw == 2 and B * sd >= 64 and T >= 64
+
+
+def fir_shape_supported(B, T, sd, dtype, var_mode, has_lengths, ws, piece=False):
+    return (dtype == F32 and var_mode == VAR_UNIT and not has_lengths and 1 <= ws.nw <= 3 and ws.mw <= 2 and ws.l[0] == 0
+            and ws.u[0] == 0 and ws.c0 != 0.0 and not piece and T >= 96 and B >= 1 and sd >= 1)
+
+
+# ---- the plan
+
+Plan = collections.namedtuple("Plan", "attempted merged members lanes cap piece piece_first alone")
+"""attempted: the call looks for a merged launch (family and variance mode allow one); merged: it makes one; members: the
+streams on its lanes in lane order (the cut stream last); lanes: [(stream, first lane, lanes)]; cap: the lanes the launch may
+hold; piece: the stream whose tail runs on its own (-1: none) from static dim piece_first on; alone: the other streams with
+static dims that run on their own launch (or a copy, for pass-through streams), in table order."""
+
+
+def merge_plan(streams, wl, wu, wc, algo, var_mode, dtype, B, T, ld_in, ld_out):
+    n_str = len(streams)
+    merge_strip = algo in (AUTO, STRIP) and var_mode == VAR_FRAME
+    merge_const = algo in (AUTO, CONST) and var_mode in (VAR_GLOBAL, VAR_UNIT)
+    attempted = merge_strip or merge_const
+    members, lanes, cap, piece, piece_first, ok = [], [], 0, -1, 0, False
+    if attempted:
+        cand, first, total = [], None, 0
+
+        def coef(s, n):
+            off = sum(int(wl[w]) + int(wu[w]) + 1 for w in range(s["win_first"]))
+            return np.asarray(wc[off:off + n], dtype=np.float64)
+
+        for k, s in enumerate(streams):
+            if s["static_dim"] <= 0 or s["num_windows"] != 3:
+                continue
+            f = s["win_first"]
+            lu = [(int(wl[f + w]), int(wu[f + w])) for w in range(3)]
+            if any(l > 1 or u > 1 for l, u in lu):
+                continue
+            nco = sum(l + u + 1 for l, u in lu)
+            if first is not None:
+                f0 = streams[first]["win_first"]
+                if lu != [(int(wl[f0 + w]), int(wu[f0 + w])) for w in range(3)]:
+                    continue
+                # memcmp: the coefficients' bytes, not their values (-0.0 != 0.0, NaN == NaN of the same payload)
+                if coef(s, nco).tobytes() != coef(streams[first], nco).tobytes():
+                    continue
+            else:
+                first = k
+            cand.append(k)
+            total += s["static_dim"]
+        cap = total
+        if total > 64 and total % 64 < 32:
+            cap = total - total % 64
+        order = sorted(cand, key=lambda k: -streams[k]["static_dim"])      # stable: widest first, table order among equals
+        pos = 0
+        for k in order:
+            if len(members) == 4:
+                break
+            sd = streams[k]["static_dim"]
+            if pos + sd > cap:
+                continue
+            members.append(k)
+            lanes.append((k, pos, sd))
+            pos += sd
+        if pos < cap and len(members) < 4:
+            for k in order:
+                if k in members:
+                    continue
+                piece, piece_first = k, cap - pos
+                members.append(k)
+                lanes.append((k, pos, piece_first))
+                pos = cap
+                break
+        n = len(members)
+        ok = n >= 2 and (pos + 63) // 64 <= n
+        if ok:
+            ws = Win(wl, wu, wc, streams[first]["win_first"], 3)
+            if merge_strip:
+                sdw = min(pos, 64)
+                ok = strip_supported(T, ws) and (algo == STRIP or strip_preferred(B, T, sdw, var_mode, ws))
+            else:
+                ok = ws.mw == 1 and (algo == CONST or B * ((pos + 63) // 64) >= 192)
+        if not ok:
+            piece, piece_first = -1, 0
+    merged_set = set(members) - {piece} if ok else set()
+    alone = [k for k in range(n_str) if streams[k]["static_dim"] > 0 and k not in merged_set]
+    return Plan(attempted, ok, members if ok else [], lanes if ok else [], cap, piece, piece_first, alone)
+
+
+class Refused(Exception):
+    """The call returns MLPG_HIP_EINVAL for a stream a forced family cannot take; str() is the family's name."""
+
+
+def solo_kind(s, ws, algo, var_mode, dtype, B, T, has_lengths, ld, sd, piece):
+    """The launch counter kind of one stream (or piece) of `sd` dims running alone under a FORCED family (capi.hip stream_entry
+    + dispatch_solve + route_of); raises Refused where the family refuses it."""
+    if piece and algo in (CONST, CHUNK, FIR):
+        algo = AUTO                                   # a piece goes to the kernels that take the window pitch separately
+    if algo == WAVE and not wave_supported(T, ws):
+        raise Refused("MLPG_HIP_ALGO_WAVE")
+    if algo == STRIP and not strip_supported(T, ws):
+        raise Refused("MLPG_HIP_ALGO_STRIP")
+    if algo == CONST and not const_supported(B, T, sd, var_mode, ws):
+        raise Refused("MLPG_HIP_ALGO_CONST")
+    if algo == CHUNK and not chunk_supported(ws):
+        raise Refused("MLPG_HIP_ALGO_CHUNK")
+    if algo == FIR and not fir_shape_supported(B, T, sd, dtype, var_mode, has_lengths, ws):
+        raise Refused("MLPG_HIP_ALGO_FIR")
+    if algo == FIR:
+        return K_FIR
+    if piece:
+        if (algo == AUTO and strip_tr_preferred(B, T, sd, ld, dtype, ws)) or \
+                (algo == STRIP and strip_tr_supported(B, T, sd, ld, ws)):
+            return K_STRIP_TR
+        return K_WAVE if wave_supported(T, ws) else K_GENERIC
+    if algo == AUTO:
+        raise ValueError("AUTO is not predicted for a whole stream")
+    if algo == STRIP:
+        return K_STRIP_TR if strip_tr_supported(B, T, sd, ld, ws) else K_STRIP
+    return {CONST: K_CONST, CHUNK: K_CHUNK, WAVE: K_WAVE, GENERIC: K_GENERIC}[algo]
+
+
+def predict(streams, wl, wu, wc, algo, var_mode, dtype, B, T, ld_in, ld_out, has_lengths):
+    """(plan, counter deltas) of one accepted call.  The deltas are a Counter of kinds -- exact for a forced family, or None
+    under AUTO, where only the merged launch (plan.merged) and the number of launches (n_launches) are fixed.  Raises Refused
+    for a forced family that a stream of the call cannot take."""
+    plan = merge_plan(streams, wl, wu, wc, algo, var_mode, dtype, B, T, ld_in, ld_out)
+    ld = max(ld_in, ld_out)
+    kinds = collections.Counter()
+    if plan.merged:
+        kinds[K_STRIP_MULTI if var_mode == VAR_FRAME else K_CONST_MULTI] += 1
+    exact = algo != AUTO
+    for k in plan.alone:
+        s = streams[k]
+        if s["num_windows"] == 0:
+            continue                                  # pass-through: a copy, no kernel family
+        ws = Win(wl, wu, wc, s["win_first"], s["num_windows"])
+        piece = k == plan.piece
+        sd = s["static_dim"] - plan.piece_first if piece else s["static_dim"]
+        if exact or piece:
+            kinds[solo_kind(s, ws, algo, var_mode, dtype, B, T, has_lengths, ld, sd, piece)] += 1
+        else:
+            kinds["auto"] += 1
+    return plan, (kinds if exact else None), sum(kinds.values())
+
