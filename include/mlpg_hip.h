@@ -97,7 +97,8 @@ void mlpg_hip_shutdown(void);
  * registers between them).  mean (B, Tmax, D), target (B, Tmax, D/nw), grad_mean (B, Tmax, D) of `dtype`; y_out
  * (B, Tmax, D/nw) or NULL; loss: one float64 on the device; n_elems: the divisor of the mean (B * Tmax * D/nw for
  * nn.MSELoss over a padded batch).  Window extents <= 1, Tmax <= 1024.  The loss is summed in a fixed order
- * (bitwise repeatable).  status as for mlpg_hip_forward (may be NULL).
+ * (bitwise repeatable).  status as for mlpg_hip_forward (may be NULL); a system whose status is non-zero gets 0 in its y and
+ * grad_mean columns and adds nothing to the loss.
  * workspace: caller-owned device memory, 128-byte aligned, >= mlpg_hip_unit_mse_workspace_bytes(B, D, nw) bytes,
  * zeroed ONCE by the caller before its first use (the kernel leaves its arrival counter zero); one workspace per stream
  * that may run the call concurrently.  The call allocates nothing and is capturable into a HIP graph.
