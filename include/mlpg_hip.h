@@ -80,7 +80,8 @@ const char *mlpg_hip_last_error(void);
  * 8 constant-coefficient with several streams merged, 9 strip in its transposed form (narrow streams: the lanes over several
  * utterances); and, counting CALLS rather than launches, 10 host-memory calls that took the short path with their inputs copied to the
  * device, 11 with the kernel reading the pinned staging buffer itself (see mlpg_hip_forward_host); 100 + d: chunks the chunked
- * host-memory calls (mlpg_hip_forward_host_multi / mlpg_hip_fastdtw_host_multi) have enqueued on device d; -1 for any other `kind`.
+ * host-memory calls (mlpg_hip_forward_host_multi / mlpg_hip_fastdtw_host_multi) have enqueued on device d; 13 launches of the
+ * variance-gradient kernel of mlpg_hip_backward_var; -1 for any other `kind` (12 included).
  * (Tests use it to assert WHICH kernel / route a call took.) */
 long long mlpg_hip_launch_count(int kind);
 int mlpg_hip_device_count(void);
@@ -309,6 +310,38 @@ int mlpg_hip_backward(int device, void *stream, int in_dtype, int out_dtype,
                       const int32_t *win_l_h, const int32_t *win_u_h,
                       const double *win_coef_h, void *grad_mean,
                       int32_t *status);
+
+/*
+ * MLPG backward w.r.t. the means AND the variances, batched: what the reference cannot do (autograd/_impl/mlpg.py:44 "we cannot
+ * do MLPG on minibatch", and its backward returns no gradient for the variances) and what training a model that predicts a
+ * variance per frame (mixture-density, heteroscedastic output layers) through MLPG needs.  For utterance b of length L and
+ * static dim d:
+ *   tau_w[t] = 1 / var[t, w*sd + d] in the input dtype; for w >= 1 zero where t < mw or t >= L - mw, mw = max_w max(l_w, u_w),
+ *   and the whole column when mw == 0 (the reference's [-0:] slice); W_w truncated at 0 and L;
+ *   P = sum_w W_w^T diag(tau_w) W_w,  y = P^-1 sum_w W_w^T (tau_w * mu_w),  g = dLoss/dy,  z = P^-1 g;
+ *   grad_mean[t, w*sd+d] = tau_w[t] (W_w z)[t]                                   (= mlpg_hip_backward)
+ *   dLoss/dtau_w[t]      = (W_w z)[t] (mu_w[t] - (W_w y)[t])
+ *   grad_var[t, w*sd+d]  = -tau_w[t]^2 (W_w z)[t] (mu_w[t] - (W_w y)[t]) = -grad_mean[t, w*sd+d] tau_w[t] (mu_w[t] - (W_w y)[t])
+ * grad_var is exactly 0 where the mask removes the precision (such var entries are never read: they may hold 0, a negative
+ * value or NaN), in rows at and past L, and in every column of a system whose status is non-zero.  Since y does not change
+ * when all variances of a system are scaled alike, sum_{w,t} var_w[t] grad_var_w[t] = 0 per system.
+ *
+ *   dtype    : MLPG_HIP_F32 or MLPG_HIP_F64 for every array; the gradients come back in it
+ *   var_mode : MLPG_HIP_VAR_FRAME or MLPG_HIP_VAR_GLOBAL (MLPG_HIP_VAR_UNIT: MLPG_HIP_EINVAL, nothing to differentiate)
+ *   mean, var: as in mlpg_hip_forward;  y (B, Tmax, sd): the trajectory mlpg_hip_forward returned for them;  grad_out (B, Tmax, sd)
+ *   grad_mean (B, Tmax, D): bit-identical to mlpg_hip_backward(dtype, dtype, algo, ...) -- the same solve by the same route
+ *   grad_var  (B, Tmax, D) in both modes; with global (D,) variances entry (b, t, c) is frame t's contribution to the gradient of
+ *             the tiled vector: the gradient of the (D,) vector is its sum over b and t (the caller sums; no library scratch)
+ *   status   : int32 (B * sd), required; filled as mlpg_hip_backward fills it
+ * algo routes the solve as in mlpg_hip_backward (a forced kernel that cannot take the problem: MLPG_HIP_EINVAL, nothing is
+ * launched); then ONE launch of the variance-gradient kernel on the same stream (mlpg_hip_launch_count(13)).  Allocates nothing
+ * beyond what the solve's route uses; capturable into a HIP graph once that route's scratch exists.
+ */
+int mlpg_hip_backward_var(int device, void *stream, int dtype, int algo,
+                          const void *mean, const void *var, int var_mode, const void *y,
+                          const void *grad_out, const int32_t *lengths, int B, int Tmax, int D,
+                          int num_windows, const int32_t *win_l_h, const int32_t *win_u_h,
+                          const double *win_coef_h, void *grad_mean, void *grad_var, int32_t *status);
 
 /*
  * The same call on HOST memory (ABI 14): the literal paramgen.mlpg_grad(mean_frames, variance_frames, windows, grad_output) of the

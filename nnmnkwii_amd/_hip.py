@@ -57,6 +57,7 @@ EXPORTS = (
     "mlpg_hip_unit_mse_form",
     "mlpg_hip_host_copy",
     "mlpg_hip_backward_host",
+    "mlpg_hip_backward_var",
 )
 
 
@@ -146,6 +147,8 @@ def lib():
                                                vp, ctypes.c_int64, vp]
         L.mlpg_hip_backward.restype = ci
         L.mlpg_hip_backward.argtypes = [ci, vp, ci, ci, ci, vp, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]
+        L.mlpg_hip_backward_var.restype = ci
+        L.mlpg_hip_backward_var.argtypes = [ci, vp, ci, ci, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
         L.mlpg_hip_delta_features.restype = ci
         L.mlpg_hip_delta_features.argtypes = [ci, vp, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp]
         L.mlpg_hip_modspec.restype = ci
@@ -608,6 +611,41 @@ def backward(var, grad_out, windows, D, lengths=None, out_dtype=None, algo=ALGO_
                                  _p(grad), _p(status))
     _check(rc, "mlpg_hip_backward")
     return grad, status
+
+
+def backward_var(mean, var, y, grad_out, windows, lengths=None, algo=ALGO_AUTO):
+    """Batched MLPG gradient w.r.t. the means AND the variances on device tensors (mlpg_hip_backward_var).
+
+    mean (B, T, D), var (B, T, D) or (D,), y (B, T, sd): the trajectory forward() returned for them, grad_out (B, T, sd); one
+    dtype (float32 / float64), contiguous, on one device; lengths: cuda int32 (B,) or None.  Returns (grad_mean (B, T, D),
+    grad_var (B, T, D), status int32 (B*sd)) in that dtype, enqueued on the current stream.  grad_mean is bit-identical to
+    backward(var, grad_out, windows, D, lengths, out_dtype=dtype, algo=algo); with (D,) variances grad_var holds each frame's
+    contribution, the gradient of the vector is its sum over (0, 1).
+    """
+    torch = torch_mod()
+    assert grad_out.is_cuda and grad_out.dim() == 3 and grad_out.is_contiguous()
+    B, T, sd = grad_out.shape
+    nw, pl, pu, pc, _keep = _win_args(windows)
+    D = sd * nw
+    assert mean.shape == (B, T, D) and mean.dtype == grad_out.dtype and mean.is_contiguous() and mean.device == grad_out.device
+    assert y.shape == (B, T, sd) and y.dtype == grad_out.dtype and y.is_contiguous() and y.device == grad_out.device
+    assert var is not None, "backward_var: unit variances have no variances to differentiate"
+    if var.dim() == 1:
+        mode = VAR_GLOBAL
+        assert var.shape[0] == D and var.dtype == grad_out.dtype and var.is_contiguous() and var.device == grad_out.device
+    else:
+        mode = VAR_FRAME
+        assert var.shape == (B, T, D) and var.dtype == grad_out.dtype and var.is_contiguous() and var.device == grad_out.device
+    if lengths is not None:
+        assert lengths.dtype == torch.int32 and lengths.shape == (B,) and lengths.device == grad_out.device
+    grad_mean = torch.empty((B, T, D), dtype=grad_out.dtype, device=grad_out.device)
+    grad_var = torch.empty((B, T, D), dtype=grad_out.dtype, device=grad_out.device)
+    status = torch.empty((B * sd,), dtype=torch.int32, device=grad_out.device)
+    rc = lib().mlpg_hip_backward_var(grad_out.device.index, _stream(grad_out.device), _dt(grad_out), algo, _p(mean), _p(var), mode,
+                                     _p(y), _p(grad_out), _p(lengths), B, T, D, nw, pl, pu, pc, _p(grad_mean), _p(grad_var),
+                                     _p(status))
+    _check(rc, "mlpg_hip_backward_var")
+    return grad_mean, grad_var, status
 
 
 def delta_features(x, windows, lengths=None):

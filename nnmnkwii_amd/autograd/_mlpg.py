@@ -8,6 +8,7 @@ drop-in compatibility and are staged through the GPU).
 import numpy as np
 import torch
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from .. import _hip
 from ..paramgen import _mlpg as G
@@ -217,6 +218,107 @@ def mlpg(means, variances, windows):
         variances = variances.expand(T, D)
     assert means.size() == variances.size()
     return MLPG.apply(means, variances, windows)
+
+
+def _lengths_on(lengths, B, T, dev):
+    """``lengths`` (None, a sequence, an ndarray or a tensor) as an int32 (B,) tensor on ``dev``.  Host values are checked
+    against [0, T]; a tensor already on the GPU is taken as it is (no synchronisation: the kernels clamp it)."""
+    if lengths is None:
+        return None
+    if torch.is_tensor(lengths):
+        L = lengths.detach().reshape(-1)
+        if not L.is_cuda:
+            host = L.numpy()
+    else:
+        host = np.asarray(lengths).reshape(-1)
+        L = None
+    if L is None or not L.is_cuda:
+        if host.shape != (B,) or not np.issubdtype(host.dtype, np.integer) or (host < 0).any() or (host > T).any():
+            raise ValueError("lengths must hold %d integers in [0, %d], got %r" % (B, T, host))
+        L = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32))
+    elif L.shape != (B,):
+        raise ValueError("lengths must have shape (%d,), got %s" % (B, tuple(L.shape)))
+    if L.dtype != torch.int32:
+        L = L.to(torch.int32)
+    return _to_gpu(L, dev)
+
+
+class MLPGBatch(Function):
+    """Batched MLPG with gradients for the means AND the variances, ``f : (B, Tmax, D), var -> (B, Tmax, static_dim)``.
+
+    What the reference cannot do (autograd/_impl/mlpg.py:44: "we cannot do MLPG on minibatch"; its backward returns no
+    gradient for the variances): a zero-padded minibatch with per-utterance ``lengths`` on the GPU, differentiable in the
+    variances -- for models that predict a variance per frame (mixture-density, heteroscedastic output layers).  ``means``
+    ``(B, Tmax, D)`` or ``(T, D)``; ``variances`` of the same shape or a global ``(D,)``, same dtype (float32 / float64); the
+    output keeps that dtype and lives on ``means.device``, rows at and past each length 0.  Forward = ``mlpg_hip_forward``;
+    backward = ``mlpg_hip_backward`` when only the means want a gradient, else ``mlpg_hip_backward_var`` (the same solve plus
+    one launch for the variance gradient; a ``(D,)`` gradient is the float64 sum of the per-frame contributions).  CPU tensors
+    are staged through the current GPU.  With ``CHECK_STATUS`` off, forward + backward capture into a CUDA graph after one eager
+    step on the capturing stream (the scratch of the solve's route must exist).
+    """
+
+    @staticmethod
+    def forward(ctx, means, variances, windows, lengths=None):
+        if means.dim() not in (2, 3):
+            raise ValueError("means must be (B, Tmax, D) or (T, D), got %s" % (tuple(means.shape),))
+        if means.dtype not in (torch.float32, torch.float64) or variances.dtype != means.dtype:
+            raise TypeError("means and variances must share one dtype, float32 or float64 (got %s, %s)" % (means.dtype, variances.dtype))
+        D = means.shape[-1]
+        if not (variances.shape == means.shape or (variances.dim() == 1 and variances.shape[0] == D)):
+            raise ValueError("variances must have the shape of means or (%d,), got %s" % (D, tuple(variances.shape)))
+        pw = _hip.cached_windows(windows)
+        if D % pw[3]:
+            raise ValueError("D=%d is not a multiple of the %d windows" % (D, pw[3]))
+        dev = _hip.require_gpu(means.device if means.is_cuda else None)
+        m, v = _to_gpu(means, dev), _to_gpu(variances, dev)
+        if means.dim() == 2:
+            m = m[None]
+            v = v if v.dim() == 1 else v[None]
+        L = _lengths_on(lengths, m.shape[0], m.shape[1], dev)
+        y, status = _hip.forward(m, v, pw, L, want_status=CHECK_STATUS)
+        if CHECK_STATUS:
+            _hip.raise_on_status(status, y.shape[-1])
+        out = y if means.dim() == 3 else y[0]
+        if out.device != means.device:
+            out = out.to(means.device)
+        ctx.windows, ctx.lengths, ctx.dev = pw, L, dev
+        ctx.save_for_backward(means, variances, out)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        means, variances, out = ctx.saved_tensors
+        need_m, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_m or need_v):
+            return None, None, None, None
+        dev, three = ctx.dev, means.dim() == 3
+        go = _to_gpu(grad_output, dev).to(means.dtype)
+        v = _to_gpu(variances, dev)
+        if not three:
+            go = go[None]
+            v = v if v.dim() == 1 else v[None]
+        gv = None
+        if need_v:
+            m, y = _to_gpu(means, dev), _to_gpu(out, dev)
+            gm, gv, _ = _hip.backward_var(m if three else m[None], v, y if three else y[None], go, ctx.windows, ctx.lengths)
+            if variances.dim() == 1:
+                # the gradient of the tiled vector: the sum of every frame's contribution (0 at padding and masked entries)
+                gv = gv.sum(dim=(0, 1), dtype=torch.float64).to(means.dtype)
+            elif not three:
+                gv = gv[0]
+            gv = _back(gv, variances)
+        else:
+            gm, _ = _hip.backward(v, go, ctx.windows, means.shape[-1], ctx.lengths, out_dtype=means.dtype, want_status=False)
+        gm = _back(gm if three else gm[0], means) if need_m else None
+        return gm, gv, None, None
+
+
+def mlpg_batch(means, variances, windows, lengths=None):
+    """Differentiable batched MLPG (:class:`MLPGBatch`): ``means`` ``(B, Tmax, D)`` or ``(T, D)``, ``variances`` of the same
+    shape or ``(D,)``, ``lengths`` None / a sequence / an ndarray / a tensor of valid frames per utterance.  Both the means and
+    the variances may require a gradient; the output keeps the input dtype."""
+    return MLPGBatch.apply(means, variances, windows, lengths)
 
 
 def unit_variance_mlpg(R, means):

@@ -397,7 +397,7 @@ __attribute__((visibility("default"))) int mlpg_hip_abi_version(void) { return 1
 
 __attribute__((visibility("default"))) long long mlpg_hip_launch_count(int kind) {
   if (kind >= 100) return host_chunks_on_device(kind - 100);  // chunks the host-memory calls enqueued on device kind - 100
-  return kind >= 0 && kind < kCountKinds ? g_launches[kind].load() : -1;
+  return kind >= 0 && kind < kCountKinds && kind != kCountUnused12 ? g_launches[kind].load() : -1;
 }
 
 __attribute__((visibility("default"))) const char *mlpg_hip_last_error(void) { return g_err; }
@@ -879,6 +879,54 @@ __attribute__((visibility("default"))) int mlpg_hip_backward(int device, void *s
                                                              int32_t *status) {
   return solve_entry(device, stream, in_dtype, out_dtype, algo, true, nullptr, var, var_mode, grad_out, lengths, B,
                      Tmax, D, num_windows, win_l_h, win_u_h, win_coef_h, grad_mean, status);
+}
+
+__attribute__((visibility("default"))) int mlpg_hip_backward_var(int device, void *stream, int dtype, int algo,
+                                                                 const void *mean, const void *var, int var_mode, const void *y,
+                                                                 const void *grad_out, const int32_t *lengths, int B, int Tmax,
+                                                                 int D, int num_windows, const int32_t *win_l_h,
+                                                                 const int32_t *win_u_h, const double *win_coef_h,
+                                                                 void *grad_mean, void *grad_var, int32_t *status) {
+  // every argument is checked here or by solve_entry before its solve is enqueued; the epilogue itself cannot be refused
+  if (int rc = check_common(B, Tmax, D, num_windows)) return rc;
+  if (dtype != MLPG_HIP_F32 && dtype != MLPG_HIP_F64) {
+    set_error("backward_var: dtype must be MLPG_HIP_F32 or MLPG_HIP_F64 (got %d)", dtype);
+    return MLPG_HIP_EINVAL;
+  }
+  if (var_mode == MLPG_HIP_VAR_UNIT) {
+    set_error("backward_var: unit variances (MLPG_HIP_VAR_UNIT) have no variances to differentiate");
+    return MLPG_HIP_EINVAL;
+  }
+  if ((var_mode != MLPG_HIP_VAR_FRAME && var_mode != MLPG_HIP_VAR_GLOBAL) || !var) {
+    set_error("backward_var: bad var_mode %d / NULL var", var_mode);
+    return MLPG_HIP_EINVAL;
+  }
+  if (!status) {
+    set_error("backward_var: status is required (int32, B * D/num_windows): a failing system's gradients are zeroed from it");
+    return MLPG_HIP_EINVAL;
+  }
+  if (B * (long)Tmax * D > 0 && (!mean || !y || !grad_out || !grad_mean || !grad_var)) {
+    set_error("backward_var: NULL data pointer (mean, y, grad_out, grad_mean and grad_var are required)");
+    return MLPG_HIP_EINVAL;
+  }
+  if (device < 0 || device >= kMaxDevices) {
+    set_error("backward_var: bad device %d", device);
+    return MLPG_HIP_EINVAL;
+  }
+  WinSet ws;
+  if (int rc = pack_windows(num_windows, win_l_h, win_u_h, win_coef_h, &ws)) return rc;
+  // the solve z = P^-1 g and grad_mean, exactly as mlpg_hip_backward(dtype, dtype, algo, ...) computes them
+  if (int rc = solve_entry(device, stream, dtype, dtype, algo, true, nullptr, var, var_mode, grad_out, lengths, B, Tmax, D,
+                           num_windows, win_l_h, win_u_h, win_coef_h, grad_mean, status))
+    return rc;
+  if (B == 0 || Tmax == 0 || D == 0) return 0;
+  DeviceGuard g(device);
+  if (!g.ok) {
+    set_error("cannot select device %d", device);
+    return MLPG_HIP_ERUNTIME;
+  }
+  return launch_var_grad((hipStream_t)stream, dtype, grad_mean, var, var_mode, mean, y, lengths, status, B, Tmax, D / num_windows,
+                         ws, grad_var);
 }
 
 __attribute__((visibility("default"))) int mlpg_hip_delta_features(int device, void *stream, int dtype, const void *x,

@@ -72,7 +72,8 @@ inline bool rows_fit_buffer(const Problem &p) {
 
 void set_error(const char *fmt, ...);
 // launches per kernel family since the library was loaded (mlpg_hip_launch_count: a test aid)
-enum { kCountGeneric = 0, kCountWave, kCountStrip, kCountStripMulti, kCountConst, kCountFused, kCountChunk, kCountFir, kCountConstMulti, kCountStripTr, kCountHostSmall, kCountHostSmallDirect, kCountKinds };
+// (kind 12 counts nothing and reads -1; 13: the variance-gradient epilogue of mlpg_hip_backward_var)
+enum { kCountGeneric = 0, kCountWave, kCountStrip, kCountStripMulti, kCountConst, kCountFused, kCountChunk, kCountFir, kCountConstMulti, kCountStripTr, kCountHostSmall, kCountHostSmallDirect, kCountUnused12, kCountVarGrad, kCountKinds };
 void note_launch(int kind);
 // Grow-only scratch, cached per (device, stream, slot): slot 0 generic factor, 1 fastdtw pyramids,
 // 2 generic status, 3 strip records, 4 constant-coefficient kernel (factor table), 5 fastdtw from host costs (D rows, back-pointers), 6 chunked kernel (records, block factors, separator solutions, marks).  Returns nullptr (and sets the error) on failure.
@@ -139,6 +140,10 @@ int launch_modspec_dft(hipStream_t s, int device, int mode, const double *x, con
                        int log_domain);
 int launch_delta(hipStream_t s, int dtype, const void *x, const int32_t *lengths, int B, int Tmax, int D,
                  const WinSet &w, void *out);
+// mlpg_vargrad.hip: grad_var from grad_mean, var, mean and y behind the backward solve (one launch, kind kCountVarGrad)
+int launch_var_grad(hipStream_t s, int dtype, const void *grad_mean, const void *var, int var_mode, const void *mean,
+                    const void *y, const int32_t *lengths, const int32_t *status, int B, int Tmax, int sd, const WinSet &w,
+                    void *grad_var);
 int launch_trim(hipStream_t s, int dtype, const void *X, int N, int T, int D, double eps, int32_t *lengths);
 int launch_fastdtw(hipStream_t s, int device, const double *X, const double *Y, const int32_t *lenx,
                    const int32_t *leny, int N, int Tx, int Ty, int D, int radius, int dist_kind, double dist_scale,

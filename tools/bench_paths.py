@@ -489,6 +489,36 @@ def _run(only, quick, device_index):
         emit(path="c2-forward-f32", ms=ms, frames_per_s=B * T / ms * 1e3, alg_bytes=by, GBps=by / ms / 1e6)
         del m32, v32
 
+    # ---- c2v: gradients w.r.t. the variances (mlpg_hip_backward_var) at config-2 scale; only with --only c2v ----
+    if args.only and "c2v" in args.only.split(","):
+        B, T, sd = 256, 1000, 60
+        for name, dt, esz in (("f64", torch.float64, 8), ("f32", torch.float32, 4)):
+            m = torch.randn(B, T, 3 * sd, dtype=dt, device=dev, generator=gen)
+            v = torch.rand(B, T, 3 * sd, dtype=dt, device=dev, generator=gen) + 0.1
+            go = torch.randn(B, T, sd, dtype=dt, device=dev, generator=gen)
+            y, _ = _hip.forward(m, v, WINDOWS, want_status=False)
+            ms_b = gpu_time(lambda: _hip.backward(v, go, WINDOWS, 3 * sd, out_dtype=dt), steps=20)
+            ms_v = gpu_time(lambda: _hip.backward_var(m, v, y, go, WINDOWS), steps=20)
+            by_b = float(esz) * (3 + 1 + 3) * sd * B * T
+            by_k = float(esz) * (4 * 3 + 1) * sd * B * T     # the new kernel: read 3 x (grad_mean, var, mean) + y, write 3 grad_var
+            share = ms_v - ms_b
+            emit(path="c2v-backward-" + name, ms=ms_b, alg_bytes=by_b, GBps=by_b / ms_b / 1e6)
+            emit(path="c2v-backward_var-" + name, ms=ms_v, alg_bytes=by_b + by_k, GBps=(by_b + by_k) / ms_v / 1e6)
+            emit(path="c2v-var-grad-kernel-share-" + name, ms=share, alg_bytes=by_k, GBps=by_k / share / 1e6 if share > 0 else None,
+                 note="HIP-event time of backward_var minus backward alone; rocprofv3 --kernel-trace gives the kernel's own duration")
+            mq = m.clone().requires_grad_()
+            vq = v.clone().requires_grad_()
+
+            def step():
+                mq.grad = None
+                vq.grad = None
+                (AF.mlpg_batch(mq, vq, WINDOWS) * go).sum().backward()
+
+            ms_s = gpu_time(step, steps=10)
+            emit(path="c2v-mlpg_batch-step-" + name, ms=ms_s, frames_per_s=B * T / ms_s * 1e3,
+                 note="autograd.mlpg_batch forward + backward, requires_grad on means and variances, CHECK_STATUS on")
+            del m, v, go, y, mq, vq
+
     # ---- c3: unit-variance autograd fwd+bwd ----
     if want("c3"):
         B, T, D = 64, 500, 180
