@@ -81,7 +81,8 @@ const char *mlpg_hip_last_error(void);
  * utterances); and, counting CALLS rather than launches, 10 host-memory calls that took the short path with their inputs copied to the
  * device, 11 with the kernel reading the pinned staging buffer itself (see mlpg_hip_forward_host); 100 + d: chunks the chunked
  * host-memory calls (mlpg_hip_forward_host_multi / mlpg_hip_fastdtw_host_multi) have enqueued on device d; 13 launches of the
- * variance-gradient kernel of mlpg_hip_backward_var; -1 for any other `kind` (12 included).
+ * variance-gradient kernel of mlpg_hip_backward_var; 15 launches of the stream-table epilogue of mlpg_hip_backward_streams; -1 for
+ * any other `kind` (12 and 14 included).
  * (Tests use it to assert WHICH kernel / route a call took.) */
 long long mlpg_hip_launch_count(int kind);
 int mlpg_hip_device_count(void);
@@ -342,6 +343,39 @@ int mlpg_hip_backward_var(int device, void *stream, int dtype, int algo,
                           const void *grad_out, const int32_t *lengths, int B, int Tmax, int D,
                           int num_windows, const int32_t *win_l_h, const int32_t *win_u_h,
                           const double *win_coef_h, void *grad_mean, void *grad_var, int32_t *status);
+
+/*
+ * Backward pass of mlpg_hip_forward_streams: the gradients of every stream of a multi-stream batch w.r.t. its means and (optionally)
+ * its variances, written IN PLACE into the streams' own columns -- no slicing copies of the batch, of grad_out or of the gradients.
+ * The stream table, the window tables and the layouts are those of mlpg_hip_forward_streams:
+ *   mean, var, grad_mean, grad_var : (B, Tmax, ld_in); var (ld_in,) for MLPG_HIP_VAR_GLOBAL, NULL for MLPG_HIP_VAR_UNIT
+ *   y, grad_out                    : (B, Tmax, ld_out), stream k at columns [out_col, out_col + static_dim); y is the trajectory
+ *                                    the forward call returned
+ *   status                         : int32 (B, sum static_dim), table order
+ *   grad_var may be NULL: only the means get a gradient, and mean and y may then be NULL too.  A non-NULL grad_var with unit
+ *   variances is MLPG_HIP_EINVAL; a non-NULL grad_var requires status.
+ * A dynamic stream runs the backward solve of mlpg_hip_backward (same routing by `algo`, same launch counter, same status) on its
+ * column slice: grad_mean columns [in_col, in_col + num_windows * static_dim), rows at and past lengths[b] zero.  A pass-through
+ * stream (num_windows == 0) gets grad_mean = grad_out on live rows and 0 on padding, grad_var = 0, status = 0; its variance columns
+ * are never read.  Columns of grad_mean / grad_var that belong to no stream are not touched.  grad_var follows the formula and the
+ * zero rules of mlpg_hip_backward_var (masked entries -- never read --, padding, every column of a failing system); with global
+ * variances it holds the per-frame contributions and the caller sums over (b, t).
+ * Every launch goes on the caller's stream: the solves in table order, then the stream-table epilogue kernel (launch counter 15) --
+ * one launch per distinct window list (win_first, num_windows) for the variance gradient of its streams, one launch for all
+ * pass-through streams.  Everything is validated before the first launch: a stream that does not fit ld_in / ld_out, more than 64
+ * streams, a bad dtype / mode / algo, or a forced `algo` that cannot take some dynamic stream (the error names the stream and the
+ * algo) return MLPG_HIP_EINVAL with nothing launched, no output byte written and no counter moved (forced MLPG_HIP_ALGO_FIR: the
+ * tap table of a window set is built on its first use, before the verdict).  Empty batches return 0.  Allocates nothing beyond the
+ * scratch of the solve routes; capturable into a HIP graph once that scratch exists.
+ */
+int mlpg_hip_backward_streams(int device, void *stream, int dtype, int algo,
+                              const void *mean, const void *var, int var_mode, int64_t ld_in,
+                              const void *y, const void *grad_out, int64_t ld_out,
+                              const int32_t *lengths, int B, int Tmax,
+                              int num_streams, const mlpg_hip_stream_t *streams_h,
+                              int total_windows, const int32_t *win_l_h, const int32_t *win_u_h,
+                              const double *win_coef_h,
+                              void *grad_mean, void *grad_var, int32_t *status);
 
 /*
  * The same call on HOST memory (ABI 14): the literal paramgen.mlpg_grad(mean_frames, variance_frames, windows, grad_output) of the

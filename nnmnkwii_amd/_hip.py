@@ -58,6 +58,7 @@ EXPORTS = (
     "mlpg_hip_host_copy",
     "mlpg_hip_backward_host",
     "mlpg_hip_backward_var",
+    "mlpg_hip_backward_streams",
 )
 
 
@@ -149,6 +150,9 @@ def lib():
         L.mlpg_hip_backward.argtypes = [ci, vp, ci, ci, ci, vp, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]
         L.mlpg_hip_backward_var.restype = ci
         L.mlpg_hip_backward_var.argtypes = [ci, vp, ci, ci, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+        L.mlpg_hip_backward_streams.restype = ci
+        L.mlpg_hip_backward_streams.argtypes = [ci, vp, ci, ci, vp, vp, ci, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, ci, ci, ci, vp,
+                                                ci, vp, vp, vp, vp, vp, vp]
         L.mlpg_hip_delta_features.restype = ci
         L.mlpg_hip_delta_features.argtypes = [ci, vp, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp]
         L.mlpg_hip_modspec.restype = ci
@@ -532,27 +536,10 @@ class StreamDesc(ctypes.Structure):
                 ("num_windows", ctypes.c_int32), ("win_first", ctypes.c_int32)]
 
 
-def forward_streams(mean, var, streams, lengths=None, algo=ALGO_AUTO, want_status=True):
-    """Multi-stream MLPG over one (B, T, ld) CUDA batch, streams consumed in place.
-
-    ``streams``: list of ``(in_col, static_dim, windows)``; ``windows`` is a list of (l, u, coeff)
-    triples, or None / [] for a pass-through stream (static columns copied).  Trajectories are
-    written side by side in table order.  Returns (out (B, T, sum static_dim), status (B, sum
-    static_dim) int32 or None).
-    """
-    torch = torch_mod()
-    assert mean.is_cuda and mean.dim() == 3 and mean.is_contiguous()
-    B, T, ld = mean.shape
-    if var is None:
-        mode = VAR_UNIT
-    elif var.dim() == 1:
-        mode = VAR_GLOBAL
-        assert var.shape[0] == ld and var.dtype == mean.dtype and var.is_contiguous() and var.device == mean.device
-    else:
-        mode = VAR_FRAME
-        assert var.shape == mean.shape and var.dtype == mean.dtype and var.is_contiguous() and var.device == mean.device
-    if lengths is not None:
-        assert lengths.dtype == torch.int32 and lengths.shape == (B,) and lengths.device == mean.device
+def _stream_table(streams):
+    """The C stream table of a ``[(in_col, static_dim, windows)]`` list (forward_streams, backward_streams): (table, packed l[],
+    u[], coeff[], number of windows, sum static_dim).  Output columns follow table order; window lists shared between streams
+    (the same list object) are packed once."""
     table = (StreamDesc * max(len(streams), 1))()
     wl_all, wu_all, wc_all = [], [], []
     seen = {}                       # window lists shared between streams are packed once
@@ -574,13 +561,85 @@ def forward_streams(mean, var, streams, lengths=None, algo=ALGO_AUTO, want_statu
     wl = np.ascontiguousarray(wl_all, dtype=np.int32)
     wu = np.ascontiguousarray(wu_all, dtype=np.int32)
     wc = np.ascontiguousarray(wc_all if wc_all else [0.0], dtype=np.float64)
+    return table, wl, wu, wc, len(wl_all), out_col
+
+
+def forward_streams(mean, var, streams, lengths=None, algo=ALGO_AUTO, want_status=True):
+    """Multi-stream MLPG over one (B, T, ld) CUDA batch, streams consumed in place.
+
+    ``streams``: list of ``(in_col, static_dim, windows)``; ``windows`` is a list of (l, u, coeff)
+    triples, or None / [] for a pass-through stream (static columns copied).  Trajectories are
+    written side by side in table order.  Returns (out (B, T, sum static_dim), status (B, sum
+    static_dim) int32 or None).
+    """
+    torch = torch_mod()
+    assert mean.is_cuda and mean.dim() == 3 and mean.is_contiguous()
+    B, T, ld = mean.shape
+    if var is None:
+        mode = VAR_UNIT
+    elif var.dim() == 1:
+        mode = VAR_GLOBAL
+        assert var.shape[0] == ld and var.dtype == mean.dtype and var.is_contiguous() and var.device == mean.device
+    else:
+        mode = VAR_FRAME
+        assert var.shape == mean.shape and var.dtype == mean.dtype and var.is_contiguous() and var.device == mean.device
+    if lengths is not None:
+        assert lengths.dtype == torch.int32 and lengths.shape == (B,) and lengths.device == mean.device
+    table, wl, wu, wc, n_win, out_col = _stream_table(streams)
     out = torch.empty((B, T, out_col), dtype=mean.dtype, device=mean.device)
     status = torch.empty((B, out_col), dtype=torch.int32, device=mean.device) if want_status else None
     rc = lib().mlpg_hip_forward_streams(mean.device.index, _stream(mean.device), _dt(mean), algo, _p(mean), _p(var), mode,
-                                        ld, _p(lengths), B, T, len(streams), ctypes.addressof(table), len(wl_all),
+                                        ld, _p(lengths), B, T, len(streams), ctypes.addressof(table), n_win,
                                         _np(wl), _np(wu), _np(wc), _p(out), out_col, _p(status))
     _check(rc, "mlpg_hip_forward_streams")
     return out, status
+
+
+def backward_streams(mean, var, y, grad_out, streams, lengths=None, algo=ALGO_AUTO, want_var=True):
+    """Backward pass of forward_streams over one (B, T, ld) CUDA batch, gradients written in place (mlpg_hip_backward_streams).
+
+    ``streams`` as in forward_streams; mean (B, T, ld), var of the same shape, (ld,) or None (unit variances: ``want_var`` must be
+    False), y and grad_out (B, T, sum static_dim): the trajectory forward_streams returned and its gradient; one dtype, contiguous,
+    on one device.  Returns (grad_mean (B, T, ld), grad_var (B, T, ld) or None, status int32 (B, sum static_dim)), enqueued on the
+    current stream.  Columns of the (B, T, ld) gradients that belong to no stream are zero.  With (ld,) variances grad_var holds
+    each frame's contribution: the gradient of the vector is its sum over (0, 1).  ``want_var=False``: only the means get a
+    gradient (mean and y are not read and may be None).
+    """
+    torch = torch_mod()
+    assert grad_out.is_cuda and grad_out.dim() == 3 and grad_out.is_contiguous()
+    B, T, ld_out = grad_out.shape
+    table, wl, wu, wc, n_win, out_col = _stream_table(streams)
+    assert out_col == ld_out
+    dev, dt = grad_out.device, grad_out.dtype
+    if var is None:
+        mode = VAR_UNIT
+        assert not want_var, "backward_streams: unit variances have no variances to differentiate"
+        ld = mean.shape[2] if mean is not None else max([c + max(len(w) if w else 0, 1) * sd for c, sd, w in streams] + [0])
+    elif var.dim() == 1:
+        mode, ld = VAR_GLOBAL, var.shape[0]
+        assert var.dtype == dt and var.is_contiguous() and var.device == dev
+    else:
+        mode, ld = VAR_FRAME, var.shape[2]
+        assert var.shape == (B, T, ld) and var.dtype == dt and var.is_contiguous() and var.device == dev
+    if want_var:
+        assert mean.shape == (B, T, ld) and mean.dtype == dt and mean.is_contiguous() and mean.device == dev
+        assert y.shape == (B, T, ld_out) and y.dtype == dt and y.is_contiguous() and y.device == dev
+    if lengths is not None:
+        assert lengths.dtype == torch.int32 and lengths.shape == (B,) and lengths.device == dev
+    # (a table that covers every column -- the Merlin layout -- needs no fill: the library writes every element of its streams)
+    covered = np.zeros(ld, dtype=bool)
+    for c, sd, w in streams:
+        covered[c:c + max(len(w) if w else 0, 1) * sd] = True
+    alloc = torch.empty if covered.all() else torch.zeros
+    grad_mean = alloc((B, T, ld), dtype=dt, device=dev)
+    grad_var = alloc((B, T, ld), dtype=dt, device=dev) if want_var else None
+    status = torch.empty((B, ld_out), dtype=torch.int32, device=dev)
+    rc = lib().mlpg_hip_backward_streams(dev.index, _stream(dev), _dt(grad_out), algo, _p(mean) if want_var else None, _p(var), mode,
+                                         ld, _p(y) if want_var else None, _p(grad_out), ld_out, _p(lengths), B, T, len(streams),
+                                         ctypes.addressof(table), n_win, _np(wl), _np(wu), _np(wc), _p(grad_mean), _p(grad_var),
+                                         _p(status))
+    _check(rc, "mlpg_hip_backward_streams")
+    return grad_mean, grad_var, status
 
 
 def backward(var, grad_out, windows, D, lengths=None, out_dtype=None, algo=ALGO_AUTO, want_status=True):

@@ -321,6 +321,98 @@ def mlpg_batch(means, variances, windows, lengths=None):
     return MLPGBatch.apply(means, variances, windows, lengths)
 
 
+def _stream_list(windows, stream_sizes, has_dynamic_features, D):
+    """paramgen.stream_list (the table of paramgen.multi_stream_mlpg's arguments) with ValueError for a bad argument."""
+    if len(stream_sizes) != len(has_dynamic_features) or sum(stream_sizes) != D:
+        raise ValueError("stream_sizes must have one entry per stream and sum to D=%d, got %r" % (D, list(stream_sizes)))
+    return G.stream_list(windows, stream_sizes, has_dynamic_features, error=ValueError)
+
+
+class MultiStreamMLPG(Function):
+    """Multi-stream MLPG over a padded batch with gradients for the means AND the variances of every stream, in place:
+    ``f : (B, Tmax, D), var -> (B, Tmax, sum static dims)`` for a Merlin-style ``mgc | lf0 | vuv | bap`` feature matrix.
+
+    The arguments are those of :func:`nnmnkwii_amd.paramgen.multi_stream_mlpg`; the value is the one it returns (forward =
+    ``mlpg_hip_forward_streams``).  Backward = ``mlpg_hip_backward_streams``: every dynamic stream's solve on its own columns of
+    the batch and one more kernel for the variance gradients and the pass-through streams -- no ``.contiguous()`` slices of the
+    means, the variances or the incoming gradient and no ``torch.cat`` of the results, which is what composing
+    :func:`mlpg_batch` per stream costs.  ``means`` ``(B, Tmax, D)`` or ``(T, D)``, float32 or float64; ``variances`` of the same
+    shape, a global ``(D,)`` or None (unit variances); the output keeps the dtype and lives on ``means.device`` (CPU tensors are
+    staged through the current GPU).  A ``(D,)`` variance gradient is the float64 sum of the per-frame contributions; a
+    pass-through stream's variances get a zero gradient.  ``CHECK_STATUS`` as in :class:`MLPGBatch`; with it off, forward +
+    backward capture into a CUDA graph after one eager step on the capturing stream.
+    """
+
+    @staticmethod
+    def forward(ctx, means, variances, windows, stream_sizes, has_dynamic_features, lengths=None):
+        if means.dim() not in (2, 3):
+            raise ValueError("means must be (B, Tmax, D) or (T, D), got %s" % (tuple(means.shape),))
+        if means.dtype not in (torch.float32, torch.float64) or (variances is not None and variances.dtype != means.dtype):
+            raise TypeError("means and variances must share one dtype, float32 or float64 (got %s, %s)"
+                            % (means.dtype, None if variances is None else variances.dtype))
+        D = means.shape[-1]
+        if variances is not None and not (variances.shape == means.shape or (variances.dim() == 1 and variances.shape[0] == D)):
+            raise ValueError("variances must have the shape of means or (%d,), got %s" % (D, tuple(variances.shape)))
+        streams = _stream_list(windows, stream_sizes, has_dynamic_features, D)
+        dev = _hip.require_gpu(means.device if means.is_cuda else None)
+        m = _to_gpu(means, dev)
+        v = None if variances is None else _to_gpu(variances, dev)
+        if means.dim() == 2:
+            m = m[None]
+            v = v if v is None or v.dim() == 1 else v[None]
+        L = _lengths_on(lengths, m.shape[0], m.shape[1], dev)
+        y, status = _hip.forward_streams(m, v, streams, L, want_status=CHECK_STATUS)
+        if CHECK_STATUS:
+            _hip.raise_on_status(status, y.shape[-1])
+        out = y if means.dim() == 3 else y[0]
+        if out.device != means.device:
+            out = out.to(means.device)
+        ctx.streams, ctx.lengths, ctx.dev, ctx.unit = streams, L, dev, variances is None
+        if variances is None:
+            ctx.save_for_backward(means, out)
+        else:
+            ctx.save_for_backward(means, variances, out)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        if ctx.unit:
+            (means, out), variances = ctx.saved_tensors, None
+        else:
+            means, variances, out = ctx.saved_tensors
+        need_m, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and variances is not None
+        if not (need_m or need_v):
+            return None, None, None, None, None, None
+        dev, three = ctx.dev, means.dim() == 3
+        go = _to_gpu(grad_output, dev).to(means.dtype)
+        m, y = _to_gpu(means, dev), _to_gpu(out, dev)
+        v = None if variances is None else _to_gpu(variances, dev)
+        if not three:
+            go, m, y = go[None], m[None], y[None]
+            v = v if v is None or v.dim() == 1 else v[None]
+        gm, gv, status = _hip.backward_streams(m, v, y, go, ctx.streams, ctx.lengths, want_var=need_v)
+        if CHECK_STATUS:
+            _hip.raise_on_status(status, go.shape[-1])
+        if need_v:
+            if variances.dim() == 1:
+                # the gradient of the tiled vector: the sum of every frame's contribution (0 at padding and masked entries)
+                gv = gv.sum(dim=(0, 1), dtype=torch.float64).to(means.dtype)
+            elif not three:
+                gv = gv[0]
+            gv = _back(gv, variances)
+        gm = _back(gm if three else gm[0], means) if need_m else None
+        return gm, gv, None, None, None, None
+
+
+def multi_stream_mlpg(inputs, variances, windows, stream_sizes, has_dynamic_features, lengths=None):
+    """Differentiable multi-stream MLPG (:class:`MultiStreamMLPG`): the arguments of
+    :func:`nnmnkwii_amd.paramgen.multi_stream_mlpg` on tensors -- ``inputs`` ``(B, Tmax, D)`` or ``(T, D)``, ``variances`` of
+    the same shape, ``(D,)`` or None, ``windows`` one window list for all dynamic streams or one per stream,
+    ``sum(stream_sizes) == D``.  Both ``inputs`` and ``variances`` may require a gradient; the output keeps the input dtype."""
+    return MultiStreamMLPG.apply(inputs, variances, windows, stream_sizes, has_dynamic_features, lengths)
+
+
 def unit_variance_mlpg(R, means):
     """Unit-variance MLPG; note the argument order ``(R, means)``
     (autograd/_impl/mlpg.py:202-217)."""

@@ -214,8 +214,9 @@ static Route route_of(int in_dtype, int out_dtype, int algo, bool backward, cons
   }
 }
 
-int dispatch_solve(hipStream_t st, int in_dtype, int out_dtype, int algo, bool backward, const Problem &p,
-                   const WinSet &ws, int device) {
+// Can the kernel family `algo` names take this problem?  Pure host logic (no device is touched): what dispatch_solve refuses before
+// it launches anything, asked beforehand by mlpg_hip_backward_streams for every stream of its table.
+static int check_algo(int in_dtype, int out_dtype, int algo, const Problem &p, const WinSet &ws) {
   if (algo < MLPG_HIP_ALGO_AUTO || algo > MLPG_HIP_ALGO_FIR) {
     set_error("unknown algo %d", algo);
     return MLPG_HIP_EINVAL;
@@ -240,6 +241,12 @@ int dispatch_solve(hipStream_t st, int in_dtype, int out_dtype, int algo, bool b
     set_error("MLPG_HIP_ALGO_FIR: unit variances, float32 in and out, no lengths, T >= 96, 1-3 windows of extent <= 2 (the first a single tap)");
     return MLPG_HIP_EINVAL;
   }
+  return 0;
+}
+
+int dispatch_solve(hipStream_t st, int in_dtype, int out_dtype, int algo, bool backward, const Problem &p,
+                   const WinSet &ws, int device) {
+  if (int rc = check_algo(in_dtype, out_dtype, algo, p, ws)) return rc;
   unsigned exclude = 0;
   for (;;) {
     switch (route_of(in_dtype, out_dtype, algo, backward, p, ws, exclude)) {
@@ -397,7 +404,7 @@ __attribute__((visibility("default"))) int mlpg_hip_abi_version(void) { return 1
 
 __attribute__((visibility("default"))) long long mlpg_hip_launch_count(int kind) {
   if (kind >= 100) return host_chunks_on_device(kind - 100);  // chunks the host-memory calls enqueued on device kind - 100
-  return kind >= 0 && kind < kCountKinds && kind != kCountUnused12 ? g_launches[kind].load() : -1;
+  return kind >= 0 && kind < kCountKinds && kind != kCountUnused12 && kind != kCountUnused14 ? g_launches[kind].load() : -1;
 }
 
 __attribute__((visibility("default"))) const char *mlpg_hip_last_error(void) { return g_err; }
@@ -927,6 +934,195 @@ __attribute__((visibility("default"))) int mlpg_hip_backward_var(int device, voi
   }
   return launch_var_grad((hipStream_t)stream, dtype, grad_mean, var, var_mode, mean, y, lengths, status, B, Tmax, D / num_windows,
                          ws, grad_var);
+}
+
+__attribute__((visibility("default"))) int mlpg_hip_backward_streams(
+    int device, void *stream, int dtype, int algo, const void *mean, const void *var, int var_mode, int64_t ld_in, const void *y,
+    const void *grad_out, int64_t ld_out, const int32_t *lengths, int B, int Tmax, int num_streams,
+    const mlpg_hip_stream_t *streams_h, int total_windows, const int32_t *win_l_h, const int32_t *win_u_h,
+    const double *win_coef_h, void *grad_mean, void *grad_var, int32_t *status) {
+  // ---- every refusal comes before the first launch: a refused call writes nothing and moves no counter ----
+  if (B < 0 || Tmax < 0 || num_streams < 0 || total_windows < 0 || ld_in < 0 || ld_out < 0 || ld_in > INT32_MAX ||
+      ld_out > INT32_MAX) {
+    set_error("backward_streams: negative or oversized size argument");
+    return MLPG_HIP_EINVAL;
+  }
+  if (dtype != MLPG_HIP_F32 && dtype != MLPG_HIP_F64) {
+    set_error("backward_streams: dtype must be MLPG_HIP_F32 or MLPG_HIP_F64 (got %d)", dtype);
+    return MLPG_HIP_EINVAL;
+  }
+  if (algo < MLPG_HIP_ALGO_AUTO || algo > MLPG_HIP_ALGO_FIR) {
+    set_error("backward_streams: unknown algo %d", algo);
+    return MLPG_HIP_EINVAL;
+  }
+  if (num_streams > 0 && !streams_h) {
+    set_error("backward_streams: NULL stream table");
+    return MLPG_HIP_EINVAL;
+  }
+  if (num_streams > kMaxStreams) {
+    set_error("backward_streams: more than 64 streams");
+    return MLPG_HIP_EINVAL;
+  }
+  long sd_total = 0;
+  bool any_dynamic = false;
+  for (int k = 0; k < num_streams; ++k) {
+    const mlpg_hip_stream_t &sm = streams_h[k];
+    const long width = (long)(sm.num_windows > 0 ? sm.num_windows : 1) * sm.static_dim;
+    if (sm.static_dim < 0 || sm.num_windows < 0 || sm.in_col < 0 || sm.out_col < 0 || sm.win_first < 0 ||
+        sm.win_first + sm.num_windows > total_windows || sm.in_col + width > ld_in ||
+        (long)sm.out_col + sm.static_dim > ld_out) {
+      set_error("backward_streams: stream %d does not fit (in_col=%d, out_col=%d, static_dim=%d, num_windows=%d)", k,
+                sm.in_col, sm.out_col, sm.static_dim, sm.num_windows);
+      return MLPG_HIP_EINVAL;
+    }
+    sd_total += sm.static_dim;
+    any_dynamic = any_dynamic || (sm.num_windows > 0 && sm.static_dim > 0);
+  }
+  if (var_mode < 0 || var_mode > 2 || (var_mode != MLPG_HIP_VAR_UNIT && !var)) {
+    set_error("backward_streams: bad var_mode %d / NULL var", var_mode);
+    return MLPG_HIP_EINVAL;
+  }
+  if (grad_var && var_mode == MLPG_HIP_VAR_UNIT) {
+    set_error("backward_streams: unit variances (MLPG_HIP_VAR_UNIT) have no variances to differentiate (pass grad_var = NULL)");
+    return MLPG_HIP_EINVAL;
+  }
+  if (grad_var && !status) {
+    set_error("backward_streams: grad_var needs status (int32, B * sum static_dim): a failing system's gradients are zeroed from it");
+    return MLPG_HIP_EINVAL;
+  }
+  if (total_windows > 0 && (!win_l_h || !win_u_h || !win_coef_h)) {
+    set_error("backward_streams: NULL window tables");
+    return MLPG_HIP_EINVAL;
+  }
+  if (device < 0 || device >= kMaxDevices) {
+    set_error("backward_streams: bad device %d", device);
+    return MLPG_HIP_EINVAL;
+  }
+  // the window list of every dynamic stream, packed once here (its extents and coefficient count are checked by the packing)
+  int status_cols[kMaxStreams];
+  for (int k = 0, c = 0; k < num_streams; ++k) { status_cols[k] = c; c += streams_h[k].static_dim; }
+  const size_t esz = dtype == MLPG_HIP_F32 ? 4 : 8;
+  static thread_local WinSet wsets[kMaxStreams];
+  static thread_local Problem probs[kMaxStreams];
+  for (int k = 0; k < num_streams; ++k) {
+    const mlpg_hip_stream_t &sm = streams_h[k];
+    if (sm.num_windows == 0) continue;
+    size_t coff = 0;
+    for (int w = 0; w < sm.win_first; ++w) {
+      if (win_l_h[w] < 0 || win_u_h[w] < 0 || win_l_h[w] > kMaxExtent || win_u_h[w] > kMaxExtent) {
+        set_error("backward_streams: window %d: extents (l=%d, u=%d) must be in [0, %d]", w, win_l_h[w], win_u_h[w], kMaxExtent);
+        return MLPG_HIP_EINVAL;
+      }
+      coff += (size_t)(win_l_h[w] + win_u_h[w] + 1);
+    }
+    if (int rc = pack_windows(sm.num_windows, win_l_h + sm.win_first, win_u_h + sm.win_first, win_coef_h + coff, &wsets[k])) return rc;
+    Problem &p = probs[k];
+    p = Problem();
+    p.mean = nullptr;
+    p.var = var ? (const char *)var + esz * (size_t)sm.in_col : nullptr;
+    p.grad_out = grad_out ? (const char *)grad_out + esz * (size_t)sm.out_col : nullptr;
+    p.lengths = lengths;
+    p.out = grad_mean ? (char *)grad_mean + esz * (size_t)sm.in_col : nullptr;
+    p.status = status ? status + status_cols[k] : nullptr;
+    p.var_mode = var_mode;
+    p.B = B;
+    p.Tmax = Tmax;
+    p.D = sm.num_windows * sm.static_dim;
+    p.sd = sm.static_dim;
+    p.pitch = 0;
+    p.ld_in = (long)ld_in;
+    p.ld_gout = (long)ld_out;
+    p.ld_out = (long)ld_in;
+    p.ld_status = (int)sd_total;
+  }
+  if (B == 0 || Tmax == 0 || sd_total == 0) return 0;
+  if (!grad_out || !grad_mean || (grad_var && any_dynamic && (!mean || !y))) {
+    set_error("backward_streams: NULL data pointer (grad_out and grad_mean are required; mean and y too when grad_var is given)");
+    return MLPG_HIP_EINVAL;
+  }
+  if (!streams_bwd_fits(B, Tmax, (int)(sd_total > INT32_MAX ? INT32_MAX : sd_total)) || sd_total > INT32_MAX) {
+    set_error("backward_streams: batch too large");
+    return MLPG_HIP_EINVAL;
+  }
+  for (int k = 0; k < num_streams; ++k) {
+    const mlpg_hip_stream_t &sm = streams_h[k];
+    if (sm.num_windows == 0 || sm.static_dim == 0) continue;
+    if (check_algo(dtype, dtype, algo, probs[k], wsets[k])) {
+      char why[400];
+      snprintf(why, sizeof(why), "%s", g_err);
+      set_error("backward_streams: stream %d: %s", k, why);
+      return MLPG_HIP_EINVAL;
+    }
+  }
+  DeviceGuard g(device);
+  if (!g.ok) {
+    set_error("cannot select device %d", device);
+    return MLPG_HIP_ERUNTIME;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (algo == MLPG_HIP_ALGO_FIR) {
+    // the one refusal the FIR form can only give with its tap table in hand (built on first use per window set): asked here for every
+    // stream, so that no stream is solved before another one is refused
+    for (int k = 0; k < num_streams; ++k) {
+      const mlpg_hip_stream_t &sm = streams_h[k];
+      if (sm.num_windows == 0 || sm.static_dim == 0) continue;
+      if (!fir_table_ready(st, device, wsets[k])) {
+        set_error("backward_streams: stream %d: MLPG_HIP_ALGO_FIR: the inverse of this window set does not decay to 2^-26 within 24 "
+                  "frames (or the stream is being captured before the tap table exists)", k);
+        return MLPG_HIP_EINVAL;
+      }
+    }
+  }
+  // ---- the solves: every dynamic stream through the backward dispatcher on its column slice, in table order, on the caller's stream
+  // (no side streams: two persistent strip grids side by side are only co-resident by construction in the forward plan) ----
+  for (int k = 0; k < num_streams; ++k) {
+    const mlpg_hip_stream_t &sm = streams_h[k];
+    if (sm.num_windows == 0 || sm.static_dim == 0) continue;
+    if (int rc = dispatch_solve(st, dtype, dtype, algo, true, probs[k], wsets[k], device)) return rc;
+  }
+  // ---- the epilogue: one launch per window list for the variance gradient, one for all pass-through streams ----
+  bool done[kMaxStreams] = {};
+  static thread_local ColTable ct;
+  for (int k = 0; k < num_streams && grad_var; ++k) {
+    const mlpg_hip_stream_t &sm = streams_h[k];
+    if (done[k] || sm.num_windows == 0 || sm.static_dim == 0) continue;
+    memset(&ct, 0, sizeof(ct));
+    for (int j = k; j < num_streams; ++j) {
+      const mlpg_hip_stream_t &sj = streams_h[j];
+      if (done[j] || sj.static_dim == 0 || sj.num_windows != sm.num_windows || sj.win_first != sm.win_first) continue;
+      done[j] = true;
+      ct.begin[ct.n] = ct.total;
+      ct.in_col[ct.n] = sj.in_col;
+      ct.out_col[ct.n] = sj.out_col;
+      ct.sd[ct.n] = sj.static_dim;
+      ct.stat_col[ct.n] = status_cols[j];
+      ct.total += sj.static_dim;
+      ++ct.n;
+    }
+    if (int rc = launch_streams_bwd(st, dtype, var_mode, grad_out, var, mean, y, lengths, status, B, Tmax, (long)ld_in, (long)ld_out,
+                                    (int)sd_total, ct, wsets[k], grad_mean, grad_var))
+      return rc;
+  }
+  memset(&ct, 0, sizeof(ct));
+  for (int k = 0; k < num_streams; ++k) {
+    const mlpg_hip_stream_t &sm = streams_h[k];
+    if (sm.num_windows != 0 || sm.static_dim == 0) continue;
+    ct.begin[ct.n] = ct.total;
+    ct.in_col[ct.n] = sm.in_col;
+    ct.out_col[ct.n] = sm.out_col;
+    ct.sd[ct.n] = sm.static_dim;
+    ct.stat_col[ct.n] = status_cols[k];
+    ct.total += sm.static_dim;
+    ++ct.n;
+  }
+  if (ct.n > 0) {
+    WinSet none;
+    memset(&none, 0, sizeof(none));
+    if (int rc = launch_streams_bwd(st, dtype, kStreamsBwdPass, grad_out, nullptr, nullptr, nullptr, lengths, status, B, Tmax,
+                                    (long)ld_in, (long)ld_out, (int)sd_total, ct, none, grad_mean, grad_var))
+      return rc;
+  }
+  return 0;
 }
 
 __attribute__((visibility("default"))) int mlpg_hip_delta_features(int device, void *stream, int dtype, const void *x,

@@ -72,8 +72,9 @@ inline bool rows_fit_buffer(const Problem &p) {
 
 void set_error(const char *fmt, ...);
 // launches per kernel family since the library was loaded (mlpg_hip_launch_count: a test aid)
-// (kind 12 counts nothing and reads -1; 13: the variance-gradient epilogue of mlpg_hip_backward_var)
-enum { kCountGeneric = 0, kCountWave, kCountStrip, kCountStripMulti, kCountConst, kCountFused, kCountChunk, kCountFir, kCountConstMulti, kCountStripTr, kCountHostSmall, kCountHostSmallDirect, kCountUnused12, kCountVarGrad, kCountKinds };
+// (kinds 12 and 14 count nothing and read -1; 13: the variance-gradient epilogue of mlpg_hip_backward_var; 15: the stream-table
+// epilogue of mlpg_hip_backward_streams)
+enum { kCountGeneric = 0, kCountWave, kCountStrip, kCountStripMulti, kCountConst, kCountFused, kCountChunk, kCountFir, kCountConstMulti, kCountStripTr, kCountHostSmall, kCountHostSmallDirect, kCountUnused12, kCountVarGrad, kCountUnused14, kCountStreamsBwd, kCountKinds };
 void note_launch(int kind);
 // Grow-only scratch, cached per (device, stream, slot): slot 0 generic factor, 1 fastdtw pyramids,
 // 2 generic status, 3 strip records, 4 constant-coefficient kernel (factor table), 5 fastdtw from host costs (D rows, back-pointers), 6 chunked kernel (records, block factors, separator solutions, marks).  Returns nullptr (and sets the error) on failure.
@@ -144,6 +145,20 @@ int launch_delta(hipStream_t s, int dtype, const void *x, const int32_t *lengths
 int launch_var_grad(hipStream_t s, int dtype, const void *grad_mean, const void *var, int var_mode, const void *mean,
                     const void *y, const int32_t *lengths, const int32_t *status, int B, int Tmax, int sd, const WinSet &w,
                     void *grad_var);
+// mlpg_streams_bwd.hip: the member streams of one epilogue launch of mlpg_hip_backward_streams, their static dims side by side on
+// a merged index (member m: [begin[m], begin[m] + sd[m])); columns are absolute in the parent arrays.  Passed by value.
+constexpr int kMaxStreams = 64;
+struct ColTable {
+  int n, total;
+  int begin[kMaxStreams], in_col[kMaxStreams], out_col[kMaxStreams], sd[kMaxStreams], stat_col[kMaxStreams];
+};
+constexpr int kStreamsBwdPass = 3;  // launch_streams_bwd's mode for pass-through members (otherwise MLPG_HIP_VAR_FRAME / _GLOBAL)
+bool streams_bwd_fits(int B, int Tmax, int total);
+// One launch (kind kCountStreamsBwd).  Dynamic members (one window list): grad_var from grad_mean, var, mean and y behind their
+// solves; pass-through members: grad_mean = grad_out (0 on padding), grad_var = 0 where given, status = 0 where given.
+int launch_streams_bwd(hipStream_t s, int dtype, int mode, const void *grad_out, const void *var, const void *mean, const void *y,
+                       const int32_t *lengths, int32_t *status, int B, int Tmax, long ld_in, long ld_out, int ld_status,
+                       const ColTable &ct, const WinSet &w, void *grad_mean, void *grad_var);
 int launch_trim(hipStream_t s, int dtype, const void *X, int N, int T, int D, double eps, int32_t *lengths);
 int launch_fastdtw(hipStream_t s, int device, const double *X, const double *Y, const int32_t *lenx,
                    const int32_t *leny, int N, int Tx, int Ty, int D, int radius, int dist_kind, double dist_scale,

@@ -173,6 +173,25 @@ def _raise_host_status(status):
                                     else "internal error: inter-workgroup wait timed out")
 
 
+def stream_list(windows, stream_sizes, has_dynamic_features, error=AssertionError):
+    """The ``[(in_col, static_dim, windows)]`` table of multi_stream_mlpg's arguments (also autograd.multi_stream_mlpg's, which
+    asks for ValueError): streams side by side, ``windows`` one list for all dynamic streams or one list per stream."""
+    per_stream = len(windows) > 0 and len(windows[0]) > 0 and isinstance(windows[0][0], (tuple, list))
+    if per_stream and len(windows) != len(stream_sizes):
+        raise error("one window list per stream expected (%d streams, %d lists)" % (len(stream_sizes), len(windows)))
+    streams, col = [], 0
+    for k, (size, dyn) in enumerate(zip(stream_sizes, has_dynamic_features)):
+        if dyn:
+            w = windows[k] if per_stream else windows
+            if size % len(w) != 0:
+                raise error("stream %d: %d columns are not a multiple of the %d windows" % (k, size, len(w)))
+            streams.append((col, size // len(w), w))
+        else:
+            streams.append((col, size, None))
+        col += size
+    return streams
+
+
 def multi_stream_mlpg(inputs, variances, windows, stream_sizes, has_dynamic_features, lengths=None,
                       algo=_hip.ALGO_AUTO, check=True, device=None):
     """MLPG over every stream of a multi-stream acoustic feature matrix in ONE call.
@@ -212,17 +231,7 @@ def multi_stream_mlpg(inputs, variances, windows, stream_sizes, has_dynamic_feat
         if two_d and v.dim() == 2:
             v = v[None]
         assert v.shape == m.shape
-    per_stream = len(windows) > 0 and len(windows[0]) > 0 and isinstance(windows[0][0], (tuple, list))
-    assert not per_stream or len(windows) == len(stream_sizes)
-    streams, col = [], 0
-    for k, (size, dyn) in enumerate(zip(stream_sizes, has_dynamic_features)):
-        if dyn:
-            w = windows[k] if per_stream else windows
-            assert size % len(w) == 0
-            streams.append((col, size // len(w), w))
-        else:
-            streams.append((col, size, None))
-        col += size
+    streams = stream_list(windows, stream_sizes, has_dynamic_features)
     L = None
     if lengths is not None:
         L = torch.as_tensor(np.asarray(lengths) if not torch.is_tensor(lengths) else lengths).to(

@@ -14,6 +14,8 @@
   ms  : modspec_smoothing / modspec (n = 4096) of a config-2 sized trajectory batch 256 x 1000 x 60, float64
   c5  : Merlin-style acoustic paramgen mgc(60)+lf0(1)+bap(5), T=2000, B=512 (1 GPU share of config 5), float64;
         per-stream dense tensors, and the three streams in place from one (B, T, 198) batch (forward_streams)
+  c5b : (only with --only c5b) forward + backward of the same (512, 2000, 198) batch with gradients for means and variances:
+        autograd.multi_stream_mlpg in place against three mlpg_batch on .contiguous() slices plus cat; the epilogue kernel's share
 
 Each line carries the GPU time (HIP events on the launch stream), the algorithmic bytes, GB/s, and a
 bounded CPU baseline from the oracle on the same host (the checker, timed like bench.py's cpu_baseline).
@@ -518,6 +520,83 @@ def _run(only, quick, device_index):
             emit(path="c2v-mlpg_batch-step-" + name, ms=ms_s, frames_per_s=B * T / ms_s * 1e3,
                  note="autograd.mlpg_batch forward + backward, requires_grad on means and variances, CHECK_STATUS on")
             del m, v, go, y, mq, vq
+
+    # ---- c5b: multi-stream MLPG forward + backward at config-5 scale, gradients in place; only with --only c5b ----
+    if args.only and "c5b" in args.only.split(","):
+        B, T = 512, 2000
+        sizes, dyn = [180, 3, 15], [True, True, True]                 # mgc 60 | lf0 1 | bap 5, three windows each: 198 columns
+        D, nsd = sum(sizes), sum(sizes) // 3
+        bounds = np.cumsum([0] + sizes).tolist()
+        streams = [(bounds[k], sizes[k] // 3, WINDOWS) for k in range(3)]
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import streamgrad64
+        for name, dt, esz in (("f64", torch.float64, 8), ("f32", torch.float32, 4)):
+            m = torch.randn(B, T, D, dtype=dt, device=dev, generator=gen)
+            vf = torch.rand(B, T, D, dtype=dt, device=dev, generator=gen) + 0.1
+            go = torch.randn(B, T, nsd, dtype=dt, device=dev, generator=gen)
+            for vname, v in (("frame", vf), ("global", vf[0, 0].clone())):
+                mq, vq = m.clone().requires_grad_(), v.clone().requires_grad_()
+
+                def step_inplace():
+                    mq.grad = None
+                    vq.grad = None
+                    AF.multi_stream_mlpg(mq, vq, WINDOWS, sizes, dyn).backward(go)
+
+                def step_composed():          # what a user writes without the in-place call: slices, one mlpg_batch per stream, cat
+                    mq.grad = None
+                    vq.grad = None
+                    ys = [AF.mlpg_batch(mq[:, :, a:b].contiguous(), vq[..., a:b].contiguous(), WINDOWS)
+                          for a, b in zip(bounds[:-1], bounds[1:])]
+                    torch.cat(ys, dim=2).backward(go)
+
+                tag = "%s-%s" % (vname, name)
+                by = float(esz) * B * T * (7 * nsd + 7 * nsd + 13 * nsd)   # forward solve, backward solve, variance-gradient epilogue
+                have = hasattr(AF, "multi_stream_mlpg")
+                for label, fn in (("inplace", step_inplace), ("composed", step_composed)):
+                    if label == "inplace" and not have:
+                        continue
+                    takes = [gpu_time(fn, steps=5) for _ in range(5)]
+                    emit(path="c5b-step-%s-%s" % (label, tag), ms=float(np.median(takes)), ms_min=min(takes), ms_max=max(takes),
+                         takes_ms=takes, frames_per_s=B * T / float(np.median(takes)) * 1e3, alg_bytes=by,
+                         GBps=by / float(np.median(takes)) / 1e6,
+                         note="forward + backward, requires_grad on means and variances, CHECK_STATUS on; 5 takes of the median of 5 steps")
+                if not have:
+                    continue
+                # the epilogue kernel's share: backward_streams with and without the variance gradient (HIP events)
+                md, vd = mq.detach(), vq.detach()
+                y, _ = _hip.forward_streams(md, vd, streams, want_status=False)
+                sh = []
+                for _ in range(5):
+                    ms_v = gpu_time(lambda: _hip.backward_streams(md, vd, y, go, streams), steps=5)
+                    ms_m = gpu_time(lambda: _hip.backward_streams(md, vd, y, go, streams, want_var=False), steps=5)
+                    sh.append(ms_v - ms_m)
+                by_k = float(esz) * B * T * 13 * nsd     # read 3 x (grad_mean, var, mean) + y, write 3 grad_var per (frame, dim)
+                share = float(np.median(sh))
+                emit(path="c5b-epilogue-kernel-share-" + tag, ms=share, ms_min=min(sh), ms_max=max(sh), takes_ms=sh, alg_bytes=by_k,
+                     GBps=by_k / share / 1e6 if share > 0 else None,
+                     note="HIP-event time of backward_streams with grad_var minus without: one launch for the three streams")
+                # spot check: the gradients of two utterances against the float64 reference (tests/streamgrad64.py)
+                step_inplace()
+                torch.cuda.synchronize()
+                sel = [0, B - 1]
+                sdicts = [dict(in_col=c, out_col=c // 3, static_dim=sd, windows=w) for c, sd, w in streams]
+                v_np = vd.cpu().numpy() if vd.dim() == 1 else vd[sel].cpu().numpy()
+                _, gm_ref, gv_ref = streamgrad64.multi_stream_grad64(md[sel].cpu().numpy(), v_np, go[sel].cpu().numpy(), sdicts)
+                gm_got = mq.grad[sel].double().cpu().numpy()
+                tol = 1e-10 if dt == torch.float64 else 3e-6
+                e_m = float(np.abs(gm_got - gm_ref).max() / np.abs(gm_ref).max())
+                if vd.dim() == 1:
+                    # (the sum runs over all 512 utterances on the GPU: compare the two utterances' own contributions instead)
+                    _, gv2, _ = _hip.backward_streams(md[sel].contiguous(), vd, y[sel].contiguous(), go[sel].contiguous(), streams)
+                    gv_got = gv2.double().cpu().numpy()
+                else:
+                    gv_got = vq.grad[sel].double().cpu().numpy()
+                e_v = float(np.abs(gv_got - gv_ref).max() / np.abs(gv_ref).max())
+                emit(path="c5b-spot-check-" + tag, grad_mean_rel_err=e_m, grad_var_rel_err=e_v, tol=tol, ok=bool(e_m <= tol and e_v <= tol),
+                     note="utterances 0 and 511 against the float64 reference, error over the largest gradient entry")
+                assert e_m <= tol and e_v <= tol, ("c5b spot check", tag, e_m, e_v)
+                del mq, vq, md, vd, y
+            del m, vf, go
 
     # ---- c3: unit-variance autograd fwd+bwd ----
     if want("c3"):
