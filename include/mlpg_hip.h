@@ -273,7 +273,9 @@ int mlpg_hip_host_copy(void *dst, const void *src, size_t bytes);
  * ordered on `stream`.  Which kernel solves a dim depends on the grouping, the
  * results agree to rounding (every kernel is held to the same parity bar).
  * Limits: 1 <= num_streams <= 64 (MLPG_HIP_EINVAL beyond), at most 4 streams
- * share one merged launch.
+ * share one merged launch.  Everything is validated before the first launch,
+ * a forced `algo` that one stream cannot take included (the error names the
+ * stream and the family): a refused call writes nothing and launches nothing.
  */
 typedef struct {
   int32_t in_col;      /* first column of the stream in mean / var rows  */

@@ -341,6 +341,24 @@ def _stream(device):
     return _raw_stream(device.index if device.index is not None else torch_mod().cuda.current_device())
 
 
+def _var_mode(var, ref, shape, D):
+    """The variance mode of a tensor argument: None -> unit variances, (D,) -> global, else per frame of `shape`; the dtype and
+    device of `ref`, contiguous."""
+    if var is None:
+        return VAR_UNIT
+    assert var.dtype == ref.dtype and var.is_contiguous() and var.device == ref.device
+    if var.dim() == 1:
+        assert var.shape[0] == D
+        return VAR_GLOBAL
+    assert var.shape == shape
+    return VAR_FRAME
+
+
+def _check_lengths(lengths, B, device):
+    if lengths is not None:
+        assert lengths.dtype == torch_mod().int32 and lengths.shape == (B,) and lengths.device == device
+
+
 def forward(mean, var, windows, lengths=None, algo=ALGO_AUTO, want_status=True):
     """Batched MLPG on device tensors.
 
@@ -353,17 +371,8 @@ def forward(mean, var, windows, lengths=None, algo=ALGO_AUTO, want_status=True):
     assert mean.is_cuda and mean.dim() == 3 and mean.is_contiguous()
     B, T, D = mean.shape
     nw, pl, pu, pc, _keep = _win_args(windows)
-    if var is None:
-        mode = VAR_UNIT
-    elif var.dim() == 1:
-        mode = VAR_GLOBAL
-        assert var.shape[0] == D and var.dtype == mean.dtype and var.is_contiguous() and var.device == mean.device
-    else:
-        mode = VAR_FRAME
-        assert var.shape == mean.shape and var.dtype == mean.dtype and var.is_contiguous()
-        assert var.device == mean.device
-    if lengths is not None:
-        assert lengths.dtype == torch.int32 and lengths.shape == (B,) and lengths.device == mean.device
+    mode = _var_mode(var, mean, mean.shape, D)
+    _check_lengths(lengths, B, mean.device)
     out = torch.empty((B, T, D // nw), dtype=mean.dtype, device=mean.device)
     status = torch.empty((B * (D // nw),), dtype=torch.int32, device=mean.device) if want_status else None
     rc = lib().mlpg_hip_forward(mean.device.index, _stream(mean.device), _dt(mean), algo, _p(mean), _p(var), mode,
@@ -418,6 +427,35 @@ def host_chunk_plan(n_items, target_items, num_devices):
 _host_gpu_seen = False     # mlpg_hip_device_count() > 0 has been seen (it does not change afterwards)
 
 
+def _host_lib():
+    """The library, for the host-pointer entry points (no torch involved): raises unless the HIP runtime sees a GPU."""
+    global _host_gpu_seen
+    L = lib()
+    if not _host_gpu_seen:
+        if L.mlpg_hip_device_count() <= 0:
+            raise HipExtensionError("nnmnkwii_amd needs an AMD GPU (none visible to the HIP runtime); there is no CPU fallback")
+        _host_gpu_seen = True
+    return L
+
+
+def _np_var(var, ref, shape, D):
+    """(variance mode, address) of a numpy variance argument: None, (D,) or `shape`; the dtype of `ref`, C-contiguous."""
+    if var is None:
+        return VAR_UNIT, None
+    assert var.dtype == ref.dtype and var.flags.c_contiguous
+    assert var.shape == ((D,) if var.ndim == 1 else shape)
+    return (VAR_GLOBAL if var.ndim == 1 else VAR_FRAME), var.ctypes.data
+
+
+def _np_lengths(lengths, B):
+    """(int32 array to keep alive, its address) of a numpy lengths argument; (None, None) without one."""
+    if lengths is None:
+        return None, None
+    lengths = np.ascontiguousarray(lengths, dtype=np.int32)
+    assert lengths.shape == (B,)
+    return lengths, lengths.ctypes.data
+
+
 def forward_host(mean, var, windows, lengths=None, algo=ALGO_AUTO, device=None):
     """Batched MLPG, numpy in -> numpy out through mlpg_hip_forward_host[_multi] (no torch involved): mean (B, T, D)
     float32/float64 C-contiguous, var same shape / (D,) / None, lengths int32 (B,) or None; device: GPU index
@@ -425,30 +463,15 @@ def forward_host(mean, var, windows, lengths=None, algo=ALGO_AUTO, device=None):
     utterance chunks are dealt round-robin, see device_list).  One device: mlpg_hip_forward_host, whose small calls
     (a single utterance: the literal paramgen.mlpg call) take the library's short path.
     Returns (out (B, T, sd) ndarray, status int32 (B, sd))."""
-    global _host_gpu_seen
-    L = lib()
-    if not _host_gpu_seen:
-        if L.mlpg_hip_device_count() <= 0:
-            raise HipExtensionError("nnmnkwii_amd needs an AMD GPU (none visible to the HIP runtime); there is no CPU fallback")
-        _host_gpu_seen = True
+    L = _host_lib()
     assert mean.ndim == 3 and mean.flags.c_contiguous and mean.dtype in (np.float32, np.float64)
     B, T, D = mean.shape
     pw = cached_windows(windows)
     nw = pw[3]
     pl, pu, pc = pw.ptrs()
     dt = F32 if mean.dtype == np.float32 else F64
-    if var is None:
-        mode, pv = VAR_UNIT, None
-    else:
-        assert var.dtype == mean.dtype and var.flags.c_contiguous
-        mode = VAR_GLOBAL if var.ndim == 1 else VAR_FRAME
-        assert var.shape == ((D,) if var.ndim == 1 else mean.shape)
-        pv = var.ctypes.data
-    plen = None
-    if lengths is not None:
-        lengths = np.ascontiguousarray(lengths, dtype=np.int32)
-        assert lengths.shape == (B,)
-        plen = lengths.ctypes.data
+    mode, pv = _np_var(var, mean, mean.shape, D)
+    lengths, plen = _np_lengths(lengths, B)
     out = np.empty((B, T, D // nw), dtype=mean.dtype)
     status = np.zeros((B, D // nw), dtype=np.int32)
     if isinstance(device, (list, tuple, np.ndarray)) or (isinstance(device, str) and device == "all"):
@@ -469,12 +492,7 @@ def backward_host(var, grad_out, windows, D, out_dtype=np.float32, lengths=None,
     float32/float64 C-contiguous, var (B, T, D) / (D,) of the same dtype / None (unit variances), lengths int32 (B,) or None.
     Returns (grad (B, T, D) of out_dtype, status int32 (B, sd)).  The literal paramgen.mlpg_grad call and the backward of
     autograd.MLPG on CPU tensors: the library's short path (see forward_host), in pieces of whole utterances."""
-    global _host_gpu_seen
-    L = lib()
-    if not _host_gpu_seen:
-        if L.mlpg_hip_device_count() <= 0:
-            raise HipExtensionError("nnmnkwii_amd needs an AMD GPU (none visible to the HIP runtime); there is no CPU fallback")
-        _host_gpu_seen = True
+    L = _host_lib()
     assert grad_out.ndim == 3 and grad_out.flags.c_contiguous and grad_out.dtype in (np.float32, np.float64)
     B, T, sd = grad_out.shape
     pw = cached_windows(windows)
@@ -484,18 +502,8 @@ def backward_host(var, grad_out, windows, D, out_dtype=np.float32, lengths=None,
     dt = F32 if grad_out.dtype == np.float32 else F64
     out_dtype = np.dtype(out_dtype)
     assert out_dtype in (np.float32, np.float64)
-    if var is None:
-        mode, pv = VAR_UNIT, None
-    else:
-        assert var.dtype == grad_out.dtype and var.flags.c_contiguous
-        mode = VAR_GLOBAL if var.ndim == 1 else VAR_FRAME
-        assert var.shape == ((D,) if var.ndim == 1 else (B, T, D))
-        pv = var.ctypes.data
-    plen = None
-    if lengths is not None:
-        lengths = np.ascontiguousarray(lengths, dtype=np.int32)
-        assert lengths.shape == (B,)
-        plen = lengths.ctypes.data
+    mode, pv = _np_var(var, grad_out, (B, T, D), D)
+    lengths, plen = _np_lengths(lengths, B)
     grad = np.empty((B, T, D), dtype=out_dtype)
     status = np.zeros((B, sd), dtype=np.int32)
     rc = L.mlpg_hip_backward_host(current_device_index(device), dt, F32 if out_dtype == np.float32 else F64, algo, pv, mode,
@@ -575,16 +583,8 @@ def forward_streams(mean, var, streams, lengths=None, algo=ALGO_AUTO, want_statu
     torch = torch_mod()
     assert mean.is_cuda and mean.dim() == 3 and mean.is_contiguous()
     B, T, ld = mean.shape
-    if var is None:
-        mode = VAR_UNIT
-    elif var.dim() == 1:
-        mode = VAR_GLOBAL
-        assert var.shape[0] == ld and var.dtype == mean.dtype and var.is_contiguous() and var.device == mean.device
-    else:
-        mode = VAR_FRAME
-        assert var.shape == mean.shape and var.dtype == mean.dtype and var.is_contiguous() and var.device == mean.device
-    if lengths is not None:
-        assert lengths.dtype == torch.int32 and lengths.shape == (B,) and lengths.device == mean.device
+    mode = _var_mode(var, mean, mean.shape, ld)
+    _check_lengths(lengths, B, mean.device)
     table, wl, wu, wc, n_win, out_col = _stream_table(streams)
     out = torch.empty((B, T, out_col), dtype=mean.dtype, device=mean.device)
     status = torch.empty((B, out_col), dtype=torch.int32, device=mean.device) if want_status else None
@@ -612,20 +612,15 @@ def backward_streams(mean, var, y, grad_out, streams, lengths=None, algo=ALGO_AU
     assert out_col == ld_out
     dev, dt = grad_out.device, grad_out.dtype
     if var is None:
-        mode = VAR_UNIT
         assert not want_var, "backward_streams: unit variances have no variances to differentiate"
         ld = mean.shape[2] if mean is not None else max([c + max(len(w) if w else 0, 1) * sd for c, sd, w in streams] + [0])
-    elif var.dim() == 1:
-        mode, ld = VAR_GLOBAL, var.shape[0]
-        assert var.dtype == dt and var.is_contiguous() and var.device == dev
     else:
-        mode, ld = VAR_FRAME, var.shape[2]
-        assert var.shape == (B, T, ld) and var.dtype == dt and var.is_contiguous() and var.device == dev
+        ld = var.shape[-1]
+    mode = _var_mode(var, grad_out, (B, T, ld), ld)
     if want_var:
         assert mean.shape == (B, T, ld) and mean.dtype == dt and mean.is_contiguous() and mean.device == dev
         assert y.shape == (B, T, ld_out) and y.dtype == dt and y.is_contiguous() and y.device == dev
-    if lengths is not None:
-        assert lengths.dtype == torch.int32 and lengths.shape == (B,) and lengths.device == dev
+    _check_lengths(lengths, B, dev)
     # (a table that covers every column -- the Merlin layout -- needs no fill: the library writes every element of its streams)
     covered = np.zeros(ld, dtype=bool)
     for c, sd, w in streams:
@@ -653,14 +648,7 @@ def backward(var, grad_out, windows, D, lengths=None, out_dtype=None, algo=ALGO_
     B, T, sd = grad_out.shape
     nw, pl, pu, pc, _keep = _win_args(windows)
     assert sd * nw == D
-    if var is None:
-        mode = VAR_UNIT
-    elif var.dim() == 1:
-        mode = VAR_GLOBAL
-        assert var.shape[0] == D and var.dtype == grad_out.dtype and var.is_contiguous()
-    else:
-        mode = VAR_FRAME
-        assert var.shape == (B, T, D) and var.dtype == grad_out.dtype and var.is_contiguous()
+    mode = _var_mode(var, grad_out, (B, T, D), D)
     if out_dtype is None:
         out_dtype = torch.float32
     grad = torch.empty((B, T, D), dtype=out_dtype, device=grad_out.device)
@@ -689,14 +677,8 @@ def backward_var(mean, var, y, grad_out, windows, lengths=None, algo=ALGO_AUTO):
     assert mean.shape == (B, T, D) and mean.dtype == grad_out.dtype and mean.is_contiguous() and mean.device == grad_out.device
     assert y.shape == (B, T, sd) and y.dtype == grad_out.dtype and y.is_contiguous() and y.device == grad_out.device
     assert var is not None, "backward_var: unit variances have no variances to differentiate"
-    if var.dim() == 1:
-        mode = VAR_GLOBAL
-        assert var.shape[0] == D and var.dtype == grad_out.dtype and var.is_contiguous() and var.device == grad_out.device
-    else:
-        mode = VAR_FRAME
-        assert var.shape == (B, T, D) and var.dtype == grad_out.dtype and var.is_contiguous() and var.device == grad_out.device
-    if lengths is not None:
-        assert lengths.dtype == torch.int32 and lengths.shape == (B,) and lengths.device == grad_out.device
+    mode = _var_mode(var, grad_out, (B, T, D), D)
+    _check_lengths(lengths, B, grad_out.device)
     grad_mean = torch.empty((B, T, D), dtype=grad_out.dtype, device=grad_out.device)
     grad_var = torch.empty((B, T, D), dtype=grad_out.dtype, device=grad_out.device)
     status = torch.empty((B * sd,), dtype=torch.int32, device=grad_out.device)

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include <mutex>
+
 #include "../../include/mlpg_hip.h"
 
 namespace mlpg {
@@ -71,6 +73,64 @@ inline bool rows_fit_buffer(const Problem &p) {
 }
 
 void set_error(const char *fmt, ...);
+
+// ---- the host layer's shared pieces (capi.hip; used by the entry points of capi.hip, streams_api.hip and host_api.hip) ----
+constexpr int kMaxDevices = 16;  // device indices the entry points accept
+// The dense problem of the rule above: mean / grad_out (B, Tmax, D | sd) in, out (B, Tmax, sd | D).
+inline Problem dense_problem(const void *mean, const void *var, const void *grad_out, const int32_t *lengths, void *out,
+                             int32_t *status, bool backward, int var_mode, int B, int Tmax, int D, int sd) {
+  Problem p;
+  p.mean = mean;
+  p.var = var;
+  p.grad_out = grad_out;
+  p.lengths = lengths;
+  p.out = out;
+  p.status = status;
+  p.var_mode = var_mode;
+  p.B = B;
+  p.Tmax = Tmax;
+  p.D = D;
+  p.sd = sd;
+  p.ld_in = D;
+  p.ld_gout = backward ? sd : 0;
+  p.ld_out = backward ? D : sd;
+  p.ld_status = sd;
+  return p;
+}
+// One-line argument checks: 0, or MLPG_HIP_EINVAL with the error text "<who>: ..." set (who: the entry point's name).
+int check_dtype(const char *who, int dtype);
+int check_var(const char *who, int var_mode, const void *var);  // var_mode in range, and an array unless the variances are unit
+int check_device(const char *who, int device);                  // device in [0, kMaxDevices): asked before the runtime is touched
+// Window tables -> WinSet (extents and the coefficient count are checked).
+int pack_windows(int nw, const int32_t *wl, const int32_t *wu, const double *wc, WinSet *ws);
+// Offset of window win_first's coefficients in a packed coefficient table; the extents of the windows in front are checked on the way.
+int coef_offset(const char *who, const int32_t *wl, const int32_t *wu, int win_first, size_t *off);
+// Makes `device` current for the scope; rc != 0 (error text set): it could not -- `DeviceGuard g(who, device); if (g.rc) return g.rc;`.
+struct DeviceGuard {
+  int prev = -1, target = -1, rc = 0;
+  DeviceGuard(const char *who, int device) : target(device) {
+    if (hipGetDevice(&prev) != hipSuccess || (device != prev && hipSetDevice(device) != hipSuccess)) {
+      set_error("%s: cannot select device %d", who, device);
+      rc = MLPG_HIP_ERUNTIME;
+    }
+  }
+  ~DeviceGuard() {
+    if (prev >= 0 && prev != target) (void)hipSetDevice(prev);
+  }
+};
+// Which kernel family takes a problem, and the launch of it (capi.hip: kernel choice in one place).  check_algo: can the family `algo`
+// names take this problem?  Pure host logic -- what dispatch_solve refuses before it launches anything.
+int check_algo(int in_dtype, int out_dtype, int algo, const Problem &p, const WinSet &ws);
+bool takes_strip_tr(int dtype, int algo, const Problem &p, const WinSet &ws);  // will dispatch_solve's first choice be the transposed strip form?
+int dispatch_solve(hipStream_t st, int in_dtype, int out_dtype, int algo, bool backward, const Problem &p, const WinSet &ws, int device);
+// Side streams for the independent streams of one multi-stream call (per device, created once; nullptr: none to be had).
+struct SideStreams {
+  static constexpr int kN = 3;
+  hipStream_t st[kN];
+  hipEvent_t fork, join[kN];
+  std::mutex mu;  // held by mlpg_hip_forward_streams while it enqueues (two host threads on one device)
+};
+SideStreams *side_streams(int device);
 // launches per kernel family since the library was loaded (mlpg_hip_launch_count: a test aid)
 // (kinds 12 and 14 count nothing and read -1; 13: the variance-gradient epilogue of mlpg_hip_backward_var; 15: the stream-table
 // epilogue of mlpg_hip_backward_streams)

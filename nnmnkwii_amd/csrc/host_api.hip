@@ -33,10 +33,6 @@
 
 namespace mlpg {
 
-int dispatch_solve(hipStream_t st, int in_dtype, int out_dtype, int algo, bool backward, const Problem &p,
-                   const WinSet &ws, int device);
-int pack_windows_public(int nw, const int32_t *wl, const int32_t *wu, const double *wc, WinSet *ws);
-
 namespace {
 
 struct HostCtx {
@@ -49,7 +45,7 @@ struct HostCtx {
   size_t dev_bytes = 0;
   bool ok = false;
 };
-constexpr int kMaxHostDevices = 16;  // device indices the host entry points accept
+constexpr int kMaxHostDevices = kMaxDevices;  // device indices the host entry points accept
 constexpr int kMaxRep = 4;           // staging contexts per device (occurrences of one device in a device list)
 constexpr int kMaxList = 32;         // entries of a device list
 HostCtx g_host[kMaxHostDevices][kMaxRep];
@@ -772,22 +768,10 @@ int host_small(int device, int dtype, int out_dtype, int algo, bool backward, co
     set_error("host call: copying the lengths failed: %s", hipGetErrorString(hipGetLastError()));
     return drained(MLPG_HIP_ERUNTIME);
   }
-  Problem p;
-  p.mean = backward ? nullptr : src;
-  p.var = var_bytes ? src + o_var : nullptr;
-  p.grad_out = backward ? src : nullptr;
-  p.lengths = len_bytes ? (const int32_t *)(src + o_len) : nullptr;
-  p.out = out_rt ? c.dev + o_out_dev : c.pin_out;  // pinned host memory: written by the kernel over PCIe
-  p.status = (int32_t *)(c.pin_out + o_status);
-  p.var_mode = var_mode;
-  p.B = B;
-  p.Tmax = Tmax;
-  p.D = D;
-  p.sd = sd;
-  p.ld_in = D;
-  p.ld_gout = backward ? sd : 0;
-  p.ld_out = backward ? D : sd;
-  p.ld_status = sd;
+  // (out: pinned host memory is written by the kernel over PCIe)
+  const Problem p = dense_problem(backward ? nullptr : src, var_bytes ? src + o_var : nullptr, backward ? src : nullptr,
+                                  len_bytes ? (const int32_t *)(src + o_len) : nullptr, out_rt ? c.dev + o_out_dev : c.pin_out,
+                                  (int32_t *)(c.pin_out + o_status), backward, var_mode, B, Tmax, D, sd);
   const double ts = tr.on ? HostTrace::now() : 0.0;
   int rc = dispatch_solve(c.st, dtype, out_dtype, algo, backward, p, ws, device);
   if (!rc && out_rt && hipMemcpyAsync(out_h, c.dev + o_out_dev, out_bytes, hipMemcpyDeviceToHost, c.st) != hipSuccess) {
@@ -893,16 +877,10 @@ __attribute__((visibility("default"))) int mlpg_hip_forward_host_multi(const int
     set_error("forward_host: bad sizes (B=%d, Tmax=%d, D=%d, num_windows=%d)", B, Tmax, D, num_windows);
     return MLPG_HIP_EINVAL;
   }
-  if (dtype != MLPG_HIP_F32 && dtype != MLPG_HIP_F64) {
-    set_error("dtype must be MLPG_HIP_F32 or MLPG_HIP_F64");
-    return MLPG_HIP_EINVAL;
-  }
-  if (var_mode < 0 || var_mode > 2 || (var_mode != MLPG_HIP_VAR_UNIT && !var_h)) {
-    set_error("bad var_mode %d / NULL var", var_mode);
-    return MLPG_HIP_EINVAL;
-  }
+  if (int rc = check_dtype("forward_host", dtype)) return rc;
+  if (int rc = check_var("forward_host", var_mode, var_h)) return rc;
   WinSet ws;
-  if (int rc = pack_windows_public(num_windows, win_l_h, win_u_h, win_coef_h, &ws)) return rc;
+  if (int rc = pack_windows(num_windows, win_l_h, win_u_h, win_coef_h, &ws)) return rc;
   if ((long)B * Tmax * D == 0) return 0;
   if (!mean_h || !out_h) {
     set_error("NULL data pointer");
@@ -962,22 +940,9 @@ __attribute__((visibility("default"))) int mlpg_hip_forward_host_multi(const int
       MLPG_HIP_CHECK(hipMemcpyAsync(d + o_var, vsrc, (size_t)nb * utt_in, hipMemcpyHostToDevice, st));
     }
     if (lengths_h) MLPG_HIP_CHECK(hipMemcpyAsync(d + o_len, lengths_h + b0, (size_t)nb * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    Problem p;
-    p.mean = d + o_mean;
-    p.var = var_mode == MLPG_HIP_VAR_UNIT ? nullptr : d + o_var;
-    p.grad_out = nullptr;
-    p.lengths = lengths_h ? (const int32_t *)(d + o_len) : nullptr;
-    p.out = d + o_out;
-    p.status = (int32_t *)(d + o_status);
-    p.var_mode = var_mode;
-    p.B = (int)nb;
-    p.Tmax = Tmax;
-    p.D = D;
-    p.sd = sd;
-    p.ld_in = D;
-    p.ld_gout = 0;
-    p.ld_out = sd;
-    p.ld_status = sd;
+    const Problem p = dense_problem(d + o_mean, var_mode == MLPG_HIP_VAR_UNIT ? nullptr : d + o_var, nullptr,
+                                    lengths_h ? (const int32_t *)(d + o_len) : nullptr, d + o_out, (int32_t *)(d + o_status), false,
+                                    var_mode, (int)nb, Tmax, D, sd);
     if (int rc = dispatch_solve(st, dtype, dtype, algo, false, p, ws, dl.dev[e])) return rc;
     void *odst = out_pinned ? (void *)((char *)out_h + (size_t)b0 * utt_out) : c.pin_out[slot];
     MLPG_HIP_CHECK(hipMemcpyAsync(odst, d + o_out, (size_t)nb * utt_out, hipMemcpyDeviceToHost, st));
@@ -1001,10 +966,7 @@ __attribute__((visibility("default"))) int mlpg_hip_forward_host(int device, int
                                                                  int num_windows, const int32_t *win_l_h,
                                                                  const int32_t *win_u_h, const double *win_coef_h,
                                                                  void *out_h, int32_t *status_h) {
-  if (device < 0 || device >= kMaxHostDevices) {
-    set_error("bad device %d", device);
-    return MLPG_HIP_EINVAL;
-  }
+  if (int rc = check_device("forward_host", device)) return rc;
   const int32_t one = device;
   return mlpg_hip_forward_host_multi(&one, 1, dtype, algo, mean_h, var_h, var_mode, lengths_h, B, Tmax, D, num_windows, win_l_h,
                                      win_u_h, win_coef_h, out_h, status_h);
@@ -1021,24 +983,16 @@ __attribute__((visibility("default"))) int mlpg_hip_backward_host(int device, in
                                                                   int B, int Tmax, int D, int num_windows, const int32_t *win_l_h,
                                                                   const int32_t *win_u_h, const double *win_coef_h, void *grad_h,
                                                                   int32_t *status_h) {
-  if (device < 0 || device >= kMaxHostDevices) {
-    set_error("bad device %d", device);
-    return MLPG_HIP_EINVAL;
-  }
+  if (int rc = check_device("backward_host", device)) return rc;
   if (B < 0 || Tmax < 0 || D < 0 || num_windows < 1 || D % num_windows != 0) {
     set_error("backward_host: bad sizes (B=%d, Tmax=%d, D=%d, num_windows=%d)", B, Tmax, D, num_windows);
     return MLPG_HIP_EINVAL;
   }
-  if ((in_dtype != MLPG_HIP_F32 && in_dtype != MLPG_HIP_F64) || (out_dtype != MLPG_HIP_F32 && out_dtype != MLPG_HIP_F64)) {
-    set_error("dtype must be MLPG_HIP_F32 or MLPG_HIP_F64");
-    return MLPG_HIP_EINVAL;
-  }
-  if (var_mode < 0 || var_mode > 2 || (var_mode != MLPG_HIP_VAR_UNIT && !var_h)) {
-    set_error("bad var_mode %d / NULL var", var_mode);
-    return MLPG_HIP_EINVAL;
-  }
+  if (int rc = check_dtype("backward_host", in_dtype)) return rc;
+  if (int rc = check_dtype("backward_host", out_dtype)) return rc;
+  if (int rc = check_var("backward_host", var_mode, var_h)) return rc;
   WinSet ws;
-  if (int rc = pack_windows_public(num_windows, win_l_h, win_u_h, win_coef_h, &ws)) return rc;
+  if (int rc = pack_windows(num_windows, win_l_h, win_u_h, win_coef_h, &ws)) return rc;
   if ((long)B * Tmax * D == 0) return 0;
   if (!grad_out_h || !grad_h) {
     set_error("NULL data pointer");
@@ -1083,10 +1037,7 @@ __attribute__((visibility("default"))) int mlpg_hip_fastdtw_host_multi(const int
     set_error("fastdtw_host: need N >= 0, Tx, Ty, D >= 1 and radius >= 1");
     return MLPG_HIP_EINVAL;
   }
-  if (dtype != MLPG_HIP_F32 && dtype != MLPG_HIP_F64) {
-    set_error("dtype must be MLPG_HIP_F32 or MLPG_HIP_F64");
-    return MLPG_HIP_EINVAL;
-  }
+  if (int rc = check_dtype("fastdtw_host", dtype)) return rc;
   if ((lenx_h == nullptr) != (leny_h == nullptr)) {
     set_error("fastdtw_host: give both length arrays or neither");
     return MLPG_HIP_EINVAL;
@@ -1197,10 +1148,7 @@ __attribute__((visibility("default"))) int mlpg_hip_fastdtw_host(int device, int
                                                                  int32_t *path_i_h, int32_t *path_j_h,
                                                                  int32_t *path_len_h, double *cost_h,
                                                                  int32_t *lenx_out_h, int32_t *leny_out_h) {
-  if (device < 0 || device >= kMaxHostDevices) {
-    set_error("bad device %d", device);
-    return MLPG_HIP_EINVAL;
-  }
+  if (int rc = check_device("fastdtw_host", device)) return rc;
   const int32_t one = device;
   return mlpg_hip_fastdtw_host_multi(&one, 1, dtype, X_h, Y_h, lenx_h, leny_h, N, Tx, Ty, D, radius, dist_kind, dist_scale,
                                      tie_rule, trim_eps, path_i_h, path_j_h, path_len_h, cost_h, lenx_out_h, leny_out_h);

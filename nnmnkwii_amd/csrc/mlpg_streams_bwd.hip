@@ -4,8 +4,8 @@
 // The parent arrays are (B, Tmax, ld_in) [mean, var, grad_mean, grad_var] and (B, Tmax, ld_out) [y, grad_out]; a ColTable
 // passed BY VALUE (kernarg segment, as WinSet is) lists the member streams of one launch: their static dims side by side on
 // a merged index j in [0, total), member m owning j in [begin[m], begin[m] + sd[m]).  One thread per (b, t, j), j fastest:
-//  * dynamic members (all of one window list): the formula, the zero rules and the order of reads of var_grad_kernel
-//    (mlpg_vargrad.hip) on strided rows --
+//  * dynamic members (all of one window list): var_grad_element (vargrad_element.h), the very body of var_grad_kernel
+//    (mlpg_vargrad.hip), on strided rows --
 //      grad_var[t, in_col + w*sd + d] = -grad_mean[..] tau_w[t] (mu_w[t] - (W_w y)[t]),  float64 arithmetic,
 //    0 at and past the length, 0 in every column of a system whose status is non-zero, 0 where the edge mask removes the
 //    precision, the mask test BEFORE the variance is read;
@@ -18,6 +18,7 @@
 // times the stencil loads and three times the threads).  Either way every row is requested once per array; whether the kernel then
 // runs at the rate of HBM is a matter of measurement.
 #include "common.h"
+#include "vargrad_element.h"
 
 namespace mlpg {
 namespace {
@@ -59,38 +60,8 @@ __global__ void __launch_bounds__(256) streams_bwd_kernel(const T *__restrict__ 
     for (int w = 0; w < ws.nw; ++w) gv[(size_t)w * sd] = (T)0;
     return;
   }
-  // the y stencil, shared by every window; taps outside [0, len) are the truncation of W_w (and never read)
-  int lmax = 0, umax = 0;
-  for (int w = 0; w < ws.nw; ++w) {
-    lmax = ws.l[w] > lmax ? ws.l[w] : lmax;
-    umax = ws.u[w] > umax ? ws.u[w] : umax;
-  }
-  const T *yb = y + (size_t)b * Tmax * ld_out + orow;
-  double ys[2 * kMaxExtent + 1];
-#pragma unroll
-  for (int k = -kMaxExtent; k <= kMaxExtent; ++k) {
-    const int tt = t + k;
-    ys[k + kMaxExtent] = (k >= -lmax && k <= umax && tt >= 0 && tt < len) ? (double)yb[(size_t)tt * ld_out] : 0.0;
-  }
-  const T one = (T)1;
-  for (int w = 0; w < ws.nw; ++w) {
-    // the edge mask and the [-0:] rule BEFORE the variance is read: a masked entry may hold 0, a negative value or NaN
-    const bool masked = w >= 1 && (ws.mw == 0 || t < ws.mw || t >= len - ws.mw);
-    double g = 0.0;
-    if (!masked) {
-      const size_t c = (size_t)w * sd;
-      const double tau = (double)(one / (MODE == MLPG_HIP_VAR_GLOBAL ? var[(size_t)ct.in_col[lo] + d + c] : var[row + c]));
-      const double *cw = ws.c + ws.off[w];
-      const int l = ws.l[w], u = ws.u[w];
-      double wy = 0.0;
-#pragma unroll
-      for (int k = -kMaxExtent; k <= kMaxExtent; ++k)
-        if (k >= -l && k <= u) wy += cw[l + k] * ys[k + kMaxExtent];
-      const double r = (double)mean[row + c] - wy;
-      g = -(double)grad_mean[row + c] * tau * r;
-    }
-    gv[(size_t)w * sd] = (T)g;
-  }
+  var_grad_element<T>(grad_mean, var, mean, y + (size_t)b * Tmax * ld_out + orow, row,
+                      MODE == MLPG_HIP_VAR_GLOBAL ? (size_t)ct.in_col[lo] + d : row, (size_t)sd, (size_t)ld_out, t, len, ws, grad_var);
 }
 
 template <typename T, int MODE>

@@ -3,11 +3,13 @@
 // For system (b, d) of length L, with tau_w = 1 / var (input dtype, edge-masked), y the trajectory and z = P^-1 g the
 // solve mlpg_hip_backward already performs (grad_mean[t, w*sd+d] = tau_w[t] (W_w z)[t]):
 //   grad_var[t, w*sd+d] = -tau_w[t]^2 (W_w z)[t] (mu_w[t] - (W_w y)[t]) = -grad_mean[t, w*sd+d] tau_w[t] (mu_w[t] - (W_w y)[t])
-// One thread per (b, t, d) handles every window: it reads the y stencil y[t - lmax .. t + umax] once (truncated at 0 and L,
-// so the padding of y is never read), then per window grad_mean, mean and -- only where the edge mask leaves the precision
-// alive -- var.  Adjacent lanes are adjacent (t, d) of the flattened (B, Tmax, sd) index, as in delta_kernel: rows are read
+// One thread per (b, t, d) handles every window (var_grad_element, vargrad_element.h: the body this kernel shares with the
+// stream-table epilogue): it reads the y stencil y[t - lmax .. t + umax] once (truncated at 0 and L, so the padding of y is never
+// read), then per window grad_mean, mean and -- only where the edge mask leaves the precision alive -- var.  Adjacent lanes are
+// adjacent (t, d) of the flattened (B, Tmax, sd) index, as in delta_kernel: rows are read
 // contiguously and narrow streams (sd = 1, 5) still fill the wavefront.  float64 arithmetic throughout.
 #include "common.h"
+#include "vargrad_element.h"
 
 namespace mlpg {
 namespace {
@@ -32,37 +34,8 @@ __global__ void __launch_bounds__(256) var_grad_kernel(const T *__restrict__ gra
     for (int w = 0; w < ws.nw; ++w) gv[(size_t)w * sd] = (T)0;
     return;
   }
-  // the y stencil, shared by every window; taps outside [0, len) are the truncation of W_w (and never read)
-  int lmax = 0, umax = 0;
-  for (int w = 0; w < ws.nw; ++w) {
-    lmax = ws.l[w] > lmax ? ws.l[w] : lmax;
-    umax = ws.u[w] > umax ? ws.u[w] : umax;
-  }
-  const T *yb = y + (size_t)b * Tmax * sd + d;
-  double ys[2 * kMaxExtent + 1];
-#pragma unroll
-  for (int k = -kMaxExtent; k <= kMaxExtent; ++k) {
-    const int tt = t + k;
-    ys[k + kMaxExtent] = (k >= -lmax && k <= umax && tt >= 0 && tt < len) ? (double)yb[(size_t)tt * sd] : 0.0;
-  }
-  const T one = (T)1;
-  for (int w = 0; w < ws.nw; ++w) {
-    // the edge mask and the [-0:] rule BEFORE the variance is read: a masked entry may hold 0, a negative value or NaN
-    const bool masked = w >= 1 && (ws.mw == 0 || t < ws.mw || t >= len - ws.mw);
-    double g = 0.0;
-    if (!masked) {
-      const double tau = (double)(one / (GLOBAL ? var[(size_t)w * sd + d] : var[row + (size_t)w * sd]));
-      const double *c = ws.c + ws.off[w];
-      const int l = ws.l[w], u = ws.u[w];
-      double wy = 0.0;
-#pragma unroll
-      for (int k = -kMaxExtent; k <= kMaxExtent; ++k)
-        if (k >= -l && k <= u) wy += c[l + k] * ys[k + kMaxExtent];
-      const double r = (double)mean[row + (size_t)w * sd] - wy;
-      g = -(double)grad_mean[row + (size_t)w * sd] * tau * r;
-    }
-    gv[(size_t)w * sd] = (T)g;
-  }
+  var_grad_element<T>(grad_mean, var, mean, y + (size_t)b * Tmax * sd + d, row, GLOBAL ? (size_t)d : row, (size_t)sd, (size_t)sd, t, len, ws,
+                      grad_var);
 }
 
 template <typename T, bool GLOBAL>

@@ -1,5 +1,5 @@
-"""The stream plan of mlpg_hip_forward_streams (nnmnkwii_amd/csrc/capi.hip) restated in plain Python, with no GPU: which
-streams share the merged launch and in which lane order, where the launch is trimmed (`cap`), which stream is cut into a head
+"""The stream plan of mlpg_hip_forward_streams (plan_streams, nnmnkwii_amd/csrc/streams_api.hip) restated in plain Python,
+with no GPU: which streams share the merged launch and in which lane order, where the launch is trimmed (`cap`), which stream is cut into a head
 and a piece, and which streams run on their own.  For forced families the launch counters the call moves are predicted
 exactly; under AUTO only the merged launch and the number of launches are.
 
@@ -130,7 +130,8 @@ def merge_plan(streams, wl, wu, wc, algo, var_mode, dtype, B, T, ld_in, ld_out):
                 f0 = streams[first]["win_first"]
                 if lu != [(int(wl[f0 + w]), int(wu[f0 + w])) for w in range(3)]:
                     continue
-                # memcmp: the coefficients' bytes, not their values (-0.0 != 0.0, NaN == NaN of the same payload)
+                # memcmp of the packed window sets: the coefficients' bytes, not their values (-0.0 != 0.0, NaN == NaN of
+                # the same payload)
                 if coef(s, nco).tobytes() != coef(streams[first], nco).tobytes():
                     continue
             else:
@@ -181,8 +182,8 @@ class Refused(Exception):
 
 
 def solo_kind(s, ws, algo, var_mode, dtype, B, T, has_lengths, ld, sd, piece):
-    """The launch counter kind of one stream (or piece) of `sd` dims running alone under a FORCED family (capi.hip stream_entry
-    + dispatch_solve + route_of); raises Refused where the family refuses it."""
+    """The launch counter kind of one stream (or piece) of `sd` dims running alone under a FORCED family (streams_api.hip stream_run
+    + capi.hip check_algo + route_of); raises Refused where the family refuses it."""
     if piece and algo in (CONST, CHUNK, FIR):
         algo = AUTO                                   # a piece goes to the kernels that take the window pitch separately
     if algo == WAVE and not wave_supported(T, ws):

@@ -71,6 +71,63 @@ def test_argument_validation_without_gpu(L):
     assert L.mlpg_hip_device_count() >= 0
 
 
+def test_device_out_of_range_is_refused_before_the_runtime_is_touched(L):
+    """Every device-pointer solve entry point answers a device outside [0, 16) with MLPG_HIP_EINVAL naming it (the pointers
+    are fakes: a call that got as far as a launch would fault)."""
+    from nnmnkwii_amd._hip import StreamDesc
+    wl = np.array([0, 1], dtype=np.int32)
+    wu = np.array([0, 1], dtype=np.int32)
+    wc = np.array([1.0, -0.5, 0.0, 0.5])
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    fake = ctypes.c_void_p(64)
+    win = (p(wl), p(wu), p(wc))
+    tab = (StreamDesc * 1)(StreamDesc(0, 0, 2, 2, 0))
+    for dev in (-1, 16, 99):
+        calls = [
+            L.mlpg_hip_forward(dev, None, 1, 0, fake, fake, 0, None, 1, 4, 4, 2, *win, fake, None),
+            L.mlpg_hip_backward(dev, None, 1, 1, 0, fake, 0, fake, None, 1, 4, 4, 2, *win, fake, None),
+            L.mlpg_hip_forward_streams(dev, None, 1, 0, fake, fake, 0, 4, None, 1, 4, 1, ctypes.addressof(tab), 2, *win, fake, 2, None),
+            L.mlpg_hip_unit_mse_form(dev, None, 0, 0, 2, 100, 4, 2, *win),
+            L.mlpg_hip_unit_mse_step(dev, None, 0, fake, fake, None, 2, 100, 4, 2, *win, 1.0, None, fake, fake, None, fake, 1 << 20),
+        ]
+        for k, rc in enumerate(calls):
+            assert rc == -1, (dev, k, rc)
+        # (each call's text, asked right behind it)
+        assert L.mlpg_hip_forward(dev, None, 1, 0, fake, fake, 0, None, 1, 4, 4, 2, *win, fake, None) == -1
+        assert b"forward: bad device" in L.mlpg_hip_last_error()
+        assert L.mlpg_hip_forward_streams(dev, None, 1, 0, fake, fake, 0, 4, None, 1, 4, 1, ctypes.addressof(tab), 2, *win, fake, 2,
+                                          None) == -1
+        assert b"forward_streams: bad device" in L.mlpg_hip_last_error()
+
+
+def test_forward_streams_refuses_a_forced_family_before_any_launch(L):
+    """A forced family one stream cannot take is answered from the plan, with no device in sight: the stream and the family
+    are named and no counter moves (mlpg_hip_backward_streams' guarantee, tests/test_backward_streams_capi_cpu.py)."""
+    from nnmnkwii_amd._hip import StreamDesc
+    wl = np.array([0, 1, 1, 2], dtype=np.int32)
+    wu = np.array([0, 1, 1, 2], dtype=np.int32)
+    wc = np.array([1.0, -0.5, 0.0, 0.5, 1.0, -2.0, 1.0, 1.0, -8.0, 0.0, 8.0, -1.0])
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    fake = ctypes.c_void_p(64)
+    tab = (StreamDesc * 2)(StreamDesc(0, 0, 4, 3, 0), StreamDesc(12, 4, 2, 1, 3))      # std windows | one window of extent 2
+
+    def call(algo, var_mode=0, Tmax=8, n=2):
+        c0 = [L.mlpg_hip_launch_count(k) for k in range(16)]
+        rc = L.mlpg_hip_forward_streams(0, None, 1, algo, fake, fake, var_mode, 14, None, 2, Tmax, n, ctypes.addressof(tab), 4,
+                                        p(wl), p(wu), p(wc), fake, 6, None)
+        assert [L.mlpg_hip_launch_count(k) for k in range(16)] == c0
+        return rc, L.mlpg_hip_last_error().decode()
+
+    for kw, word in [(dict(algo=3), "stream 1: MLPG_HIP_ALGO_STRIP"),                 # extent 2
+                     (dict(algo=2), "stream 1: MLPG_HIP_ALGO_WAVE"),
+                     (dict(algo=2, Tmax=4000, n=1), "stream 0: MLPG_HIP_ALGO_WAVE"),  # beyond 2048 frames
+                     (dict(algo=5), "stream 0: MLPG_HIP_ALGO_CONST"),                 # per-frame variances
+                     (dict(algo=7), "stream 0: MLPG_HIP_ALGO_FIR"),
+                     (dict(algo=9), "algo")]:
+        rc, err = call(**kw)
+        assert rc == -1 and word in err, (kw, rc, err)
+
+
 def test_unit_mse_form_validates_without_gpu(L):
     wl = np.array([0, 1], dtype=np.int32)
     wu = np.array([0, 1], dtype=np.int32)

@@ -1,4 +1,4 @@
-"""The restated stream plan (tests/stream_plan.py) on the layouts the comments of capi.hip mlpg_hip_forward_streams work by
+"""The restated stream plan (tests/stream_plan.py) on the layouts the comments of streams_api.hip plan_streams work by
 hand.  No GPU: this pins the restatement that tests/test_stream_routes_gpu.py predicts launch counters with."""
 import numpy as np
 import pytest

@@ -11,7 +11,7 @@ of a fixed bit pattern and the status array 0x5A5A5A5A.  In every accepted cell:
 - every other output column keeps the sentinel bit for bit;
 - every status cell is written: the oracle's verdict in the stream's table-order column, 0 for pass-through streams.
 Some cells put a negative variance into one system of a merged member, a piece or a stream that runs alone.  Refused calls
-leave counters, output and status untouched, or name the family that refused; calls stay ordered on the caller's stream and
+leave counters, output and status untouched, and name the family that refused; calls stay ordered on the caller's stream and
 replay bit-identically from a captured graph."""
 import collections
 import ctypes
@@ -431,8 +431,9 @@ def test_refused_tables_launch_nothing_and_touch_nothing():
     ("mixed_ext1", F, True, SP.CHUNK),      # std3: extent 1 is fine, static / zero2 have none
 ])
 def test_forced_family_refusal_names_the_family_and_leaves_the_stream_usable(lname, mode, ragged, algo):
-    """A family one stream of the call cannot take: EINVAL naming the family.  The next valid call on the same torch stream
-    is correct (no fork or join event left dangling)."""
+    """A family one stream of the call cannot take: EINVAL naming the family, before anything is enqueued -- no counter moves,
+    output and status keep their sentinels.  The next valid call on the same torch stream is correct (no fork or join event
+    left dangling)."""
     import torch
     lay = layout(lname)
     dt = f64
@@ -444,6 +445,7 @@ def test_forced_family_refusal_names_the_family_and_leaves_the_stream_usable(lna
     with torch.cuda.stream(s):
         rc, out, status, moved, err = drive(lay, dev(M), dev(V), mode, dev(lens), algo)
         assert rc == -1 and str(ei.value) in err, (rc, err)
+        assert moved == {} and _untouched(out, status, dt), (err, moved)
         rc, out, status, moved, err = drive(lay, dev(M), dev(V), mode, dev(lens), SP.AUTO)
         assert rc == 0, err
     check_counters(lay, moved, SP.AUTO, mode, dt, 6, 300, ragged)
