@@ -81,8 +81,10 @@ const char *mlpg_hip_last_error(void);
  * utterances); and, counting CALLS rather than launches, 10 host-memory calls that took the short path with their inputs copied to the
  * device, 11 with the kernel reading the pinned staging buffer itself (see mlpg_hip_forward_host); 100 + d: chunks the chunked
  * host-memory calls (mlpg_hip_forward_host_multi / mlpg_hip_fastdtw_host_multi) have enqueued on device d; 13 launches of the
- * variance-gradient kernel of mlpg_hip_backward_var; 15 launches of the stream-table epilogue of mlpg_hip_backward_streams; -1 for
- * any other `kind` (12 and 14 included).
+ * variance-gradient kernel of mlpg_hip_backward_var; 15 launches of the stream-table epilogue of mlpg_hip_backward_streams; 17
+ * launches of the typed in-LDS FFT kernel of mlpg_hip_modspec_batch / mlpg_hip_modspec_batch_backward, 18 transforms those two
+ * calls sent through the direct transform, 19 launches of the fused loss kernel of mlpg_hip_modspec_loss_step; -1 for
+ * any other `kind` (12, 14 and 16 included).
  * (Tests use it to assert WHICH kernel / route a call took.) */
 long long mlpg_hip_launch_count(int kind);
 int mlpg_hip_device_count(void);
@@ -445,6 +447,47 @@ int mlpg_hip_modspec_backward(int device, void *stream, const double *x,
 /* Testing aid: on != 0 routes every DFT length through the direct transform
  * (process-wide), so that tests can compare it with the FFT path. */
 void mlpg_hip_modspec_set_direct(int on);
+
+/*
+ * The modulation spectrum over a PADDED MINIBATCH, float32 or float64, and the fused log-MS loss step -- what follows the
+ * batched MLPG calls in trajectory training:  loss = mse(y, target) + w * mse(log MS(y), log MS(target)).  The reference has
+ * no such call: autograd/_impl/modspec.py:9-72 and preprocessing/modspec.py:6-53 take one (T, D) array, so a minibatch is a
+ * Python loop over utterances.  `dtype` as in mlpg_hip_forward; x, ms, grad_ms, target_ms and grad_x are all of that dtype
+ * (loaded and stored as such, arithmetic in float64).  All pointers are device pointers; every argument is checked before a
+ * device is selected or anything is launched (MLPG_HIP_EINVAL, the text names the entry point); B == 0 or D == 0 returns 0 and
+ * touches nothing.
+ *   x        : (B, Tmax, D); Tmax is the row count and may exceed n
+ *   lengths  : int32[B] or NULL (every utterance has Tmax frames).  Utterance b contributes the frames
+ *              t < min(lengths[b], n, Tmax), as rfft(x[:len], n) with its crop at n.  What lies in the padding is never read.
+ *   ms, grad_ms, target_ms : (B, n/2+1, D)
+ *   grad_x   : (B, Tmax, D); EVERY row is written -- the gradient for live frames, 0 from min(lengths[b], n) on
+ * Routes: a power of two n <= 4096 takes the in-LDS FFT kernel (mlpg_hip_launch_count(17)), any other n -- or every n after
+ * mlpg_hip_modspec_set_direct(1) -- the direct transform (kind 18; at most 65535 utterances per call).
+ *
+ * mlpg_hip_modspec_loss_step (kind 19): with P = MS(x), f(P) = log(P + eps) (log_domain != 0) or P,
+ *   loss   = sum (f(P) - f(target_ms))^2 / n_elems                        one float64
+ *   grad_x = d loss / d x = backward of g = 2 (f(P) - f(target_ms)) f'(P) / n_elems
+ * in one launch that keeps the spectrum in LDS (forward FFT, residual, inverse FFT) plus one small launch that adds the
+ * workgroups' partial sums in a fixed order: the loss is the same bit for bit on every call.  `workspace`: at least
+ * mlpg_hip_modspec_loss_workspace_bytes(B, D) bytes, 8-byte aligned, owned by the caller, content irrelevant, not to be shared
+ * by calls that may overlap.  n_elems is normally B * (n/2+1) * D.  mlpg_hip_modspec_loss_form(n): 1 when the step takes this
+ * n (a power of two in [2, 4096] on the FFT route), 0 when the caller has to compose mlpg_hip_modspec_batch, its own loss
+ * and mlpg_hip_modspec_batch_backward (any other n; every n after mlpg_hip_modspec_set_direct(1)).
+ */
+int mlpg_hip_modspec_batch(int device, void *stream, int dtype, const void *x,
+                           const int32_t *lengths, int B, int Tmax, int D, int n,
+                           int ortho, void *ms);
+int mlpg_hip_modspec_batch_backward(int device, void *stream, int dtype,
+                                    const void *x, const void *grad_ms,
+                                    const int32_t *lengths, int B, int Tmax, int D,
+                                    int n, int ortho, void *grad_x);
+int mlpg_hip_modspec_loss_form(int n);
+size_t mlpg_hip_modspec_loss_workspace_bytes(int B, int D);
+int mlpg_hip_modspec_loss_step(int device, void *stream, int dtype, const void *x,
+                               const void *target_ms, const int32_t *lengths, int B,
+                               int Tmax, int D, int n, int ortho, int log_domain,
+                               double eps, double n_elems, void *grad_x, double *loss,
+                               void *workspace, size_t workspace_bytes);
 
 /*
  * Trailing-zero trim.  Replaces preprocessing.trim_zeros_frames with trim="b"

@@ -40,6 +40,11 @@ EXPORTS = (
     "mlpg_hip_modspec_smoothing",
     "mlpg_hip_modspec_backward",
     "mlpg_hip_modspec_set_direct",
+    "mlpg_hip_modspec_batch",
+    "mlpg_hip_modspec_batch_backward",
+    "mlpg_hip_modspec_loss_form",
+    "mlpg_hip_modspec_loss_workspace_bytes",
+    "mlpg_hip_modspec_loss_step",
     "mlpg_hip_trim_lengths",
     "mlpg_hip_fastdtw",
     "mlpg_hip_forward_host_multi",
@@ -165,6 +170,16 @@ def lib():
         L.mlpg_hip_modspec_backward.argtypes = [ci, vp, vp, vp, ci, ci, ci, ci, ci, vp]
         L.mlpg_hip_modspec_set_direct.restype = None
         L.mlpg_hip_modspec_set_direct.argtypes = [ci]
+        L.mlpg_hip_modspec_batch.restype = ci
+        L.mlpg_hip_modspec_batch.argtypes = [ci, vp, ci, vp, vp, ci, ci, ci, ci, ci, vp]
+        L.mlpg_hip_modspec_batch_backward.restype = ci
+        L.mlpg_hip_modspec_batch_backward.argtypes = [ci, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp]
+        L.mlpg_hip_modspec_loss_form.restype = ci
+        L.mlpg_hip_modspec_loss_form.argtypes = [ci]
+        L.mlpg_hip_modspec_loss_workspace_bytes.restype = ctypes.c_size_t
+        L.mlpg_hip_modspec_loss_workspace_bytes.argtypes = [ci, ci]
+        L.mlpg_hip_modspec_loss_step.restype = ci
+        L.mlpg_hip_modspec_loss_step.argtypes = [ci, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, cd, cd, vp, vp, vp, ctypes.c_size_t]
         L.mlpg_hip_trim_lengths.restype = ci
         L.mlpg_hip_trim_lengths.argtypes = [ci, vp, ci, vp, ci, ci, ci, cd, vp]
         L.mlpg_hip_fastdtw_l2.restype = ci
@@ -757,6 +772,77 @@ def modspec_backward(x, grad_ms, n, ortho=False):
     _check(lib().mlpg_hip_modspec_backward(x.device.index, _stream(x.device), _p(x), _p(g), B, T, D, int(n), int(bool(ortho)),
                                            _p(out)), "mlpg_hip_modspec_backward")
     return out
+
+
+def _batch_args(x, lengths):
+    assert x.is_cuda and x.dim() == 3 and x.is_contiguous()
+    _check_lengths(lengths, x.shape[0], x.device)
+    return x.shape
+
+
+def modspec_batch(x, n, ortho=False, lengths=None):
+    """Power of the n-point DFT along time of a padded (B, Tmax, D) CUDA batch, float32 or float64, used in place
+    (mlpg_hip_modspec_batch): utterance b contributes its first min(lengths[b], n) frames.  Returns ms (B, n/2+1, D) of x's dtype."""
+    torch = torch_mod()
+    B, T, D = _batch_args(x, lengths)
+    ms = torch.empty((B, n // 2 + 1, D), dtype=x.dtype, device=x.device)
+    _check(lib().mlpg_hip_modspec_batch(x.device.index, _stream(x.device), _dt(x), _p(x), _p(lengths), B, T, D, int(n),
+                                        int(bool(ortho)), _p(ms)), "mlpg_hip_modspec_batch")
+    return ms
+
+
+def modspec_batch_backward(x, grad_ms, n, ortho=False, lengths=None):
+    """Gradient of modspec_batch w.r.t. x (mlpg_hip_modspec_batch_backward): x (B, Tmax, D), grad_ms (B, n/2+1, D) of the same
+    dtype -> (B, Tmax, D), every row written by the kernel (0 at and past each length)."""
+    torch = torch_mod()
+    B, T, D = _batch_args(x, lengths)
+    assert grad_ms.shape == (B, n // 2 + 1, D) and grad_ms.dtype == x.dtype and grad_ms.device == x.device and grad_ms.is_contiguous()
+    out = torch.empty_like(x)
+    _check(lib().mlpg_hip_modspec_batch_backward(x.device.index, _stream(x.device), _dt(x), _p(x), _p(grad_ms), _p(lengths), B, T, D,
+                                                 int(n), int(bool(ortho)), _p(out)), "mlpg_hip_modspec_batch_backward")
+    return out
+
+
+def modspec_loss_form(n):
+    """mlpg_hip_modspec_loss_form: 1 when mlpg_hip_modspec_loss_step takes the DFT length n, 0 when the caller composes the loss."""
+    return int(lib().mlpg_hip_modspec_loss_form(int(n)))
+
+
+_MS_LOSS_WORKSPACE = {}       # (device, stream) -> uint8 tensor (mlpg_hip_modspec_loss_workspace_bytes; the content is irrelevant)
+
+
+def _ms_loss_workspace(device, B, D):
+    """The per-(device, stream) workspace of mlpg_hip_modspec_loss_step, grown geometrically (as _mse_workspace).  An outgrown
+    tensor goes back to torch's allocator, which hands it out again behind the work of the stream it was allocated on."""
+    torch = torch_mod()
+    need = int(lib().mlpg_hip_modspec_loss_workspace_bytes(B, D))
+    stream = _stream(device)
+    key = (device.index, stream)
+    ws = _MS_LOSS_WORKSPACE.get(key)
+    if ws is None or ws.numel() < need:
+        size = need if ws is None else max(need, ws.numel() * 3 // 2)
+        ws = _MS_LOSS_WORKSPACE[key] = torch.empty((size + 4095) // 4096 * 4096, dtype=torch.uint8, device=device)
+    return ws, stream
+
+
+def modspec_loss_step(x, target_ms, n, ortho=False, lengths=None, log_domain=True, eps=1e-10, n_elems=None):
+    """Fused modulation-spectrum loss step on device tensors (mlpg_hip_modspec_loss_step): x (B, Tmax, D), target_ms
+    (B, n/2+1, D), float32 or float64.  Returns (loss float64 0-dim tensor = sum (f(MS(x)) - f(target_ms))^2 / n_elems,
+    grad_x (B, Tmax, D) = d loss / d x); f = log(. + eps) or the identity.  n must be one modspec_loss_form answers 1 for."""
+    torch = torch_mod()
+    B, T, D = _batch_args(x, lengths)
+    assert target_ms.shape == (B, n // 2 + 1, D) and target_ms.dtype == x.dtype and target_ms.device == x.device and \
+        target_ms.is_contiguous()
+    if n_elems is None:
+        n_elems = float(B * (n // 2 + 1) * D)
+    grad = torch.empty_like(x)
+    loss = torch.empty((), dtype=torch.float64, device=x.device)
+    ws, stream = _ms_loss_workspace(x.device, B, D)
+    rc = lib().mlpg_hip_modspec_loss_step(x.device.index, stream, _dt(x), _p(x), _p(target_ms), _p(lengths), B, T, D, int(n),
+                                          int(bool(ortho)), int(bool(log_domain)), float(eps), float(n_elems), _p(grad), _p(loss),
+                                          _p(ws), ws.numel())
+    _check(rc, "mlpg_hip_modspec_loss_step")
+    return loss, grad
 
 
 def trim_lengths(X, eps=1e-7):

@@ -12,19 +12,13 @@ from torch.autograd.function import once_differentiable
 
 from .. import _hip
 from ..paramgen import _mlpg as G
+from ._common import _lengths_on, _to_gpu  # noqa: F401
 
 # Reading the per-system status word costs one device synchronisation per call;
 # it is what turns a non-positive-definite system into the reference's
 # LinAlgError.  Training loops that know their variances are positive can turn
 # it off.
 CHECK_STATUS = True
-
-
-def _to_gpu(t, dev):
-    t = t.detach()
-    if t.device != dev:
-        t = t.to(dev)
-    return t if t.is_contiguous() else t.contiguous()
 
 
 def _back(t, like):
@@ -218,29 +212,6 @@ def mlpg(means, variances, windows):
         variances = variances.expand(T, D)
     assert means.size() == variances.size()
     return MLPG.apply(means, variances, windows)
-
-
-def _lengths_on(lengths, B, T, dev):
-    """``lengths`` (None, a sequence, an ndarray or a tensor) as an int32 (B,) tensor on ``dev``.  Host values are checked
-    against [0, T]; a tensor already on the GPU is taken as it is (no synchronisation: the kernels clamp it)."""
-    if lengths is None:
-        return None
-    if torch.is_tensor(lengths):
-        L = lengths.detach().reshape(-1)
-        if not L.is_cuda:
-            host = L.numpy()
-    else:
-        host = np.asarray(lengths).reshape(-1)
-        L = None
-    if L is None or not L.is_cuda:
-        if host.shape != (B,) or not np.issubdtype(host.dtype, np.integer) or (host < 0).any() or (host > T).any():
-            raise ValueError("lengths must hold %d integers in [0, %d], got %r" % (B, T, host))
-        L = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32))
-    elif L.shape != (B,):
-        raise ValueError("lengths must have shape (%d,), got %s" % (B, tuple(L.shape)))
-    if L.dtype != torch.int32:
-        L = L.to(torch.int32)
-    return _to_gpu(L, dev)
 
 
 class MLPGBatch(Function):

@@ -25,6 +25,9 @@ void note_launch(int kind) {
   if (kind >= 0 && kind < kCountKinds) g_launches[kind].fetch_add(1);
 }
 
+std::atomic<bool> g_modspec_direct{false};  // mlpg_hip_modspec_set_direct
+bool modspec_direct() { return g_modspec_direct; }
+
 // ---- grow-only scratch, one set of buffers per (device, stream) ------------------------------
 // Launches on different streams of one device never share a buffer; a buffer is only ever
 // reused, grown or freed behind work of its own stream.
@@ -321,7 +324,7 @@ __attribute__((visibility("default"))) int mlpg_hip_abi_version(void) { return 1
 
 __attribute__((visibility("default"))) long long mlpg_hip_launch_count(int kind) {
   if (kind >= 100) return host_chunks_on_device(kind - 100);  // chunks the host-memory calls enqueued on device kind - 100
-  return kind >= 0 && kind < kCountKinds && kind != kCountUnused12 && kind != kCountUnused14 ? g_launches[kind].load() : -1;
+  return kind >= 0 && kind < kCountKinds && kind != kCountUnused12 && kind != kCountUnused14 && kind != kCountUnused16 ? g_launches[kind].load() : -1;
 }
 
 __attribute__((visibility("default"))) const char *mlpg_hip_last_error(void) { return g_err; }
@@ -550,7 +553,6 @@ __attribute__((visibility("default"))) int mlpg_hip_delta_features(int device, v
 }
 
 namespace {
-std::atomic<bool> g_modspec_direct{false};
 int modspec_entry(int device, void *stream, int mode, const double *x, const double *ms, const double *ph, double *out,
                   double *out_ph, int B, int T, int D, int n, int ortho, int limit_bin, int log_domain) {
   if (B < 0 || T < 0 || D < 0 || n < 1) {

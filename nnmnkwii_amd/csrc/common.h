@@ -133,8 +133,9 @@ struct SideStreams {
 SideStreams *side_streams(int device);
 // launches per kernel family since the library was loaded (mlpg_hip_launch_count: a test aid)
 // (kinds 12 and 14 count nothing and read -1; 13: the variance-gradient epilogue of mlpg_hip_backward_var; 15: the stream-table
-// epilogue of mlpg_hip_backward_streams)
-enum { kCountGeneric = 0, kCountWave, kCountStrip, kCountStripMulti, kCountConst, kCountFused, kCountChunk, kCountFir, kCountConstMulti, kCountStripTr, kCountHostSmall, kCountHostSmallDirect, kCountUnused12, kCountVarGrad, kCountUnused14, kCountStreamsBwd, kCountKinds };
+// epilogue of mlpg_hip_backward_streams; 16 counts nothing and reads -1; 17: the typed in-LDS FFT kernel of mlpg_hip_modspec_batch /
+// _batch_backward; 18: their direct transform; 19: the fused loss kernel of mlpg_hip_modspec_loss_step)
+enum { kCountGeneric = 0, kCountWave, kCountStrip, kCountStripMulti, kCountConst, kCountFused, kCountChunk, kCountFir, kCountConstMulti, kCountStripTr, kCountHostSmall, kCountHostSmallDirect, kCountUnused12, kCountVarGrad, kCountUnused14, kCountStreamsBwd, kCountUnused16, kCountModspecBatch, kCountModspecBatchDft, kCountModspecLoss, kCountKinds };
 void note_launch(int kind);
 // Grow-only scratch, cached per (device, stream, slot): slot 0 generic factor, 1 fastdtw pyramids,
 // 2 generic status, 3 strip records, 4 constant-coefficient kernel (factor table), 5 fastdtw from host costs (D rows, back-pointers), 6 chunked kernel (records, block factors, separator solutions, marks).  Returns nullptr (and sets the error) on failure.
@@ -199,6 +200,15 @@ void host_api_shutdown();  // host_api.hip: streams, events, pinned and device s
 int launch_modspec_dft(hipStream_t s, int device, int mode, const double *x, const double *ms, const double *ph,
                        double *out, double *out_ph, int B, int T, int D, int n, int ortho, int limit_bin,
                        int log_domain);
+// padded minibatches, float32 / float64 (modspec_api.hip): mode 0 spectrum, 1 gradient (aux: grad_ms), 2 -- FFT form only -- the fused
+// loss step (aux: target_ms; partial: one double per workgroup, B * ceil(D / 2); loss: one double)
+bool modspec_fft_takes(int n);  // a power of two in [2, 4096]: the in-LDS FFT
+bool modspec_direct();          // mlpg_hip_modspec_set_direct's switch
+int launch_modspec_batch(hipStream_t s, int mode, int dtype, const void *x, const void *aux, const int32_t *lengths, void *out,
+                         int B, int Tmax, int D, int n, int ortho, int log_domain, double eps, double n_elems, double *partial,
+                         double *loss);
+int launch_modspec_dft_batch(hipStream_t s, int device, int mode, int dtype, const void *x, const void *grad_ms,
+                             const int32_t *lengths, void *out, int B, int Tmax, int D, int n, int ortho);
 int launch_delta(hipStream_t s, int dtype, const void *x, const int32_t *lengths, int B, int Tmax, int D,
                  const WinSet &w, void *out);
 // mlpg_vargrad.hip: grad_var from grad_mean, var, mean and y behind the backward solve (one launch, kind kCountVarGrad)

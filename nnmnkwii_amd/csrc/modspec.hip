@@ -72,11 +72,47 @@ __device__ __forceinline__ void fft_regs(Cplx (&v)[1 << LOGR]) {
   }
 }
 
+// The radix-16 first pass for the kernels of the padded-minibatch entries, in two sweeps over the thread's own 16 consecutive
+// elements (no barrier between them): stages 0-1 on four groups of four, stages 2-3 on the elements j, j+4, j+8, j+12.  The same
+// butterflies as fft_regs<4>, with 4 instead of 16 complex values live at a time: next to the typed loads and stores and the loss
+// arithmetic, 16 live values push those kernels past the 128 registers a 1024-thread workgroup leaves a lane.
+template <bool INV>
+__device__ __forceinline__ void fft16_two_sweeps(Cplx *a, int q) {
+  constexpr double c16[8] = {1.0, 0.92387953251128673848, 0.70710678118654752440, 0.38268343236508977173,
+                             0.0, -0.38268343236508977173, -0.70710678118654752440, -0.92387953251128673848};
+  constexpr double s16[8] = {0.0, 0.38268343236508977173, 0.70710678118654752440, 0.92387953251128673848,
+                             1.0, 0.92387953251128673848, 0.70710678118654752440, 0.38268343236508977173};
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    Cplx v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = a[pidx(16 * q + 4 * g + k)];
+    fft_regs<2, INV>(v);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a[pidx(16 * q + 4 * g + k)] = v[k];
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int p0 = pidx(16 * q + j), p1 = pidx(16 * q + j + 4), p2 = pidx(16 * q + j + 8), p3 = pidx(16 * q + j + 12);
+    const Cplx e0 = a[p0], e1 = a[p1], e2 = a[p2], e3 = a[p3];
+    const Cplx w1 = {c16[2 * j], INV ? s16[2 * j] : -s16[2 * j]};  // W_8^j
+    const Cplx wa = {c16[j], INV ? s16[j] : -s16[j]}, wb = {c16[j + 4], INV ? s16[j + 4] : -s16[j + 4]};
+    const Cplx t1 = j == 0 ? e1 : cmul(e1, w1), t3 = j == 0 ? e3 : cmul(e3, w1);
+    const Cplx f0 = cadd(e0, t1), f1 = csub(e0, t1), f2 = cadd(e2, t3), f3 = csub(e2, t3);
+    const Cplx g2 = j == 0 ? f2 : cmul(f2, wa), g3 = cmul(f3, wb);
+    a[p0] = cadd(f0, g2);
+    a[p2] = csub(f0, g2);
+    a[p1] = cadd(f1, g3);
+    a[p3] = csub(f1, g3);
+  }
+}
+
 // In-place FFT of the n elements at a[pidx(.)] (already in bit-reversed order).  INV: conjugated
 // twiddles (no scaling).  First pass: radix 16 (radix 8 when log2 n is odd) in registers; then
 // radix-4 passes.  tw: the per-pass tables described above (built by build_twiddles).
-template <bool INV>
-__device__ void fft_inplace(Cplx *a, const Cplx *tw, int n, int logn, int tid) {
+// SWEEPS: the radix-16 pass as fft16_two_sweeps.
+template <bool INV, bool SWEEPS>
+__device__ __forceinline__ void fft_inplace_body(Cplx *a, const Cplx *tw, int n, int logn, int tid) {
   int s0;
   if (logn < 3) {  // n = 2 or 4: plain radix-2 stages by one thread each
     for (int t = 0; t < logn; ++t) {
@@ -105,6 +141,10 @@ __device__ void fft_inplace(Cplx *a, const Cplx *tw, int n, int logn, int tid) {
     s0 = 3;
   } else {
     for (int q = tid; q < n / 16; q += kFftThreads) {
+      if (SWEEPS) {
+        fft16_two_sweeps<INV>(a, q);
+        continue;
+      }
       Cplx v[16];
 #pragma unroll
       for (int k = 0; k < 16; ++k) v[k] = a[pidx(16 * q + k)];
@@ -139,6 +179,11 @@ __device__ void fft_inplace(Cplx *a, const Cplx *tw, int n, int logn, int tid) {
     }
     __syncthreads();
   }
+}
+
+template <bool INV>
+__device__ void fft_inplace(Cplx *a, const Cplx *tw, int n, int logn, int tid) {
+  fft_inplace_body<INV, false>(a, tw, n, logn, tid);
 }
 
 // forward twiddles of every radix-4 pass of an n-point transform (see tw_offset); < n entries in total
@@ -354,6 +399,211 @@ int launch_modspec(hipStream_t st, int mode, const double *x, const double *ms, 
   }
   set_error("modspec: bad mode %d", mode);
   return MLPG_HIP_EINVAL;
+}
+
+// ---- padded minibatches, typed (mlpg_hip_modspec_batch, _batch_backward, _loss_step) -----------------------------------
+// What a training loop needs behind the batched MLPG nodes and the reference does not have (autograd/_impl/modspec.py:9-72 and
+// preprocessing/modspec.py:6-53 take ONE (T, D) array): the same workgroup per (utterance, pair of columns) and the same FFT,
+// with x loaded and the result stored as float32 or float64 (arithmetic in float64), an optional per-utterance length, and the
+// whole log-MS loss step as one mode.  Utterance b contributes the frames t < live = min(lengths[b], n, Tmax) -- rfft(x[:len], n)
+// with its crop at n; a row at or past `live` is never loaded.  The gradient modes write every row of grad_x: the value below
+// `live`, 0 from there to Tmax (the row stride; Tmax > n is fine).
+//
+// kBatchLoss, per workgroup:  z = x1 + i x2 -> FFT -> S1, S2 (unpack2, forward scale) -> P = |S|^2, Pt = target_ms ->
+//   r = f(P) - f(Pt), f = log(. + eps) | identity -> sum r^2 (registers -> wave shuffle -> 16 doubles of LDS -> partial[wg]);
+//   g = 2 r f'(P) / n_elems -> Hermitian g S (interior bins halved, edge bins real: the backward mode's rule) -> pack2 ->
+//   bit reversal -> inverse FFT -> grad_x.  Nothing but x, target_ms and grad_x touches HBM.  modspec_loss_finalize then adds
+//   the partials in a fixed order (one workgroup, strided sums, LDS tree) and writes sum / n_elems: repeatable bit for bit.
+namespace {
+
+enum { kBatchSpec = 0, kBatchBackward = 1, kBatchLoss = 2 };
+
+struct BatchArgs {
+  const void *x;           // (B, Tmax, D) of TX
+  const void *aux;         // backward: grad_ms, loss: target_ms -- (B, n/2+1, D) of TX
+  const int32_t *lengths;  // int32[B] or NULL
+  void *out;               // spec: ms (B, n/2+1, D); backward / loss: grad_x (B, Tmax, D) -- of TX
+  double *partial;         // loss: sum of r^2 per workgroup
+  int B, T, D, n, logn;    // T: Tmax, the row count of x and grad_x
+  int ortho, log_domain;
+  double eps, inv_elems;   // loss: 1 / n_elems
+};
+
+template <int MODE, typename TX>
+__global__ __launch_bounds__(kFftThreads) void modspec_batch_kernel(BatchArgs p) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  __shared__ double red[kFftThreads / 64];
+  Cplx *a = (Cplx *)smem;
+  Cplx *tw = a + padded_len(p.n);
+  const int tid = threadIdx.x;
+  const int npair = (p.D + 1) / 2;
+  const int d = 2 * (blockIdx.x % npair), b = blockIdx.x / npair;
+  const bool two = d + 1 < p.D;  // the last pair of an odd D holds one column
+  const int n = p.n, logn = p.logn, nb = n / 2 + 1, T = p.T, D = p.D;
+  const double fwd_scale = p.ortho ? 1.0 / sqrt((double)n) : 1.0;
+  int live = T < n ? T : n;
+  if (p.lengths) {
+    const int len = p.lengths[b];
+    live = len < live ? (len > 0 ? len : 0) : live;
+  }
+
+  build_twiddles(tw, logn, tid);
+
+  const TX *xb = (const TX *)p.x + (size_t)b * T * D + d;
+  for (int t = tid; t < n; t += kFftThreads) {
+    Cplx z = {0.0, 0.0};
+    if (t < live) {
+      z.re = (double)xb[(size_t)t * D];
+      if (two) z.im = (double)xb[(size_t)t * D + 1];
+    }
+    a[pidx(bitrev(t, logn))] = z;
+  }
+  __syncthreads();
+  fft_inplace_body<false, true>(a, tw, n, logn, tid);
+
+  if (MODE == kBatchSpec) {
+    TX *ob = (TX *)p.out + (size_t)b * nb * D + d;
+    for (int k = tid; k < nb; k += kFftThreads) {
+      Cplx s1, s2;
+      unpack2(a[pidx(k)], a[pidx((n - k) & (n - 1))], &s1, &s2);
+      s1 = {s1.re * fwd_scale, s1.im * fwd_scale};
+      s2 = {s2.re * fwd_scale, s2.im * fwd_scale};
+      ob[(size_t)k * D] = (TX)(s1.re * s1.re + s1.im * s1.im);
+      if (two) ob[(size_t)k * D + 1] = (TX)(s2.re * s2.re + s2.im * s2.im);
+    }
+    return;
+  }
+
+  // one thread per bin pair (k, n-k): Z' = H1 + i H2 of the Hermitian spectra g S of both columns
+  const TX *gb = (const TX *)p.aux + (size_t)b * nb * D + d;
+  double rsum = 0.0;
+  for (int k = tid; k < nb; k += kFftThreads) {
+    const int km = (n - k) & (n - 1);
+    Cplx s1, s2;
+    unpack2(a[pidx(k)], a[pidx(km)], &s1, &s2);
+    s1 = {s1.re * fwd_scale, s1.im * fwd_scale};
+    s2 = {s2.re * fwd_scale, s2.im * fwd_scale};
+    double g1 = (double)gb[(size_t)k * D], g2 = two ? (double)gb[(size_t)k * D + 1] : 0.0;
+    if (MODE == kBatchLoss) {
+      // g1, g2 hold the target powers: r = f(P) - f(Pt), g = 2 r f'(P) / n_elems
+      const double p1 = s1.re * s1.re + s1.im * s1.im, p2 = s2.re * s2.re + s2.im * s2.im;
+      double r1, r2, f1 = 1.0, f2 = 1.0;
+      if (p.log_domain) {
+        r1 = log(p1 + p.eps) - log(g1 + p.eps);
+        r2 = log(p2 + p.eps) - log(g2 + p.eps);
+        f1 = 1.0 / (p1 + p.eps);
+        f2 = 1.0 / (p2 + p.eps);
+      } else {
+        r1 = p1 - g1;
+        r2 = p2 - g2;
+      }
+      if (!two) r2 = 0.0;
+      rsum += r1 * r1 + r2 * r2;
+      g1 = 2.0 * r1 * f1 * p.inv_elems;
+      g2 = 2.0 * r2 * f2 * p.inv_elems;
+    }
+    const bool edge = k == 0 || k == n / 2;
+    const double f = edge ? 1.0 : 0.5;
+    const Cplx h1 = {f * g1 * s1.re, edge ? 0.0 : f * g1 * s1.im};
+    const Cplx h2 = two ? Cplx{f * g2 * s2.re, edge ? 0.0 : f * g2 * s2.im} : Cplx{0.0, 0.0};
+    Cplx zk, zm;
+    pack2(h1, h2, &zk, &zm);
+    a[pidx(k)] = zk;
+    if (km != k) a[pidx(km)] = zm;
+  }
+  if (MODE == kBatchLoss) {
+    // fixed order: lanes of a wave by xor shuffles, then the 16 wave sums by thread 0
+    for (int off = 32; off > 0; off >>= 1) rsum += __shfl_xor(rsum, off, 64);
+    if ((tid & 63) == 0) red[tid >> 6] = rsum;
+  }
+  __syncthreads();
+  if (MODE == kBatchLoss && tid == 0) {
+    double s = 0.0;
+    for (int w = 0; w < kFftThreads / 64; ++w) s += red[w];
+    p.partial[blockIdx.x] = s;
+  }
+  // the inverse transform wants bit-reversed input: permute in place (swap pairs)
+  for (int k = tid; k < n; k += kFftThreads) {
+    const int r = bitrev(k, logn);
+    if (r > k) {  // (member by member: a struct temporary of the swap would be the kernel's only private memory)
+      const double kre = a[pidx(k)].re, kim = a[pidx(k)].im, rre = a[pidx(r)].re, rim = a[pidx(r)].im;
+      a[pidx(k)] = {rre, rim};
+      a[pidx(r)] = {kre, kim};
+    }
+  }
+  __syncthreads();
+  fft_inplace_body<true, true>(a, tw, n, logn, tid);
+  TX *ob = (TX *)p.out + (size_t)b * T * D + d;
+  const double osc = p.ortho ? 2.0 / sqrt((double)n) : 2.0;  // C of autograd/_impl/modspec.py:47-49
+  for (int t = tid; t < T; t += kFftThreads) {
+    const bool on = t < live;  // (live <= n: a[] is only read inside the transform)
+    ob[(size_t)t * D] = (TX)(on ? a[pidx(t)].re * osc : 0.0);
+    if (two) ob[(size_t)t * D + 1] = (TX)(on ? a[pidx(t)].im * osc : 0.0);
+  }
+}
+
+// loss = (sum of the workgroups' partial sums) / n_elems, in one fixed order: thread i adds partial[i], partial[i + 256], ...,
+// then a tree over the 256 sums
+__global__ __launch_bounds__(256) void modspec_loss_finalize(const double *partial, int count, double inv_elems, double *loss) {
+  __shared__ double s[256];
+  const int tid = threadIdx.x;
+  double acc = 0.0;
+  for (int i = tid; i < count; i += 256) acc += partial[i];
+  s[tid] = acc;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (tid < h) s[tid] += s[tid + h];
+    __syncthreads();
+  }
+  if (tid == 0) *loss = s[0] * inv_elems;
+}
+
+template <int MODE, typename TX>
+int launch_batch_mode(hipStream_t st, const BatchArgs &p) {
+  const size_t lds = sizeof(Cplx) * ((size_t)padded_len(p.n) + (size_t)p.n);  // data + per-pass twiddle tables (< n entries)
+  auto kern = modspec_batch_kernel<MODE, TX>;
+  MLPG_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, dim3((unsigned)(p.B * ((p.D + 1) / 2))), dim3(kFftThreads), lds, st, p);
+  MLPG_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+template <typename TX>
+int launch_batch_typed(hipStream_t st, int mode, const BatchArgs &p) {
+  switch (mode) {
+    case kBatchSpec: return launch_batch_mode<kBatchSpec, TX>(st, p);
+    case kBatchBackward: return launch_batch_mode<kBatchBackward, TX>(st, p);
+    case kBatchLoss: return launch_batch_mode<kBatchLoss, TX>(st, p);
+  }
+  set_error("modspec_batch: bad mode %d", mode);
+  return MLPG_HIP_EINVAL;
+}
+
+}  // namespace
+
+bool modspec_fft_takes(int n) { return n >= 2 && n <= 4096 && !(n & (n - 1)); }
+
+int launch_modspec_batch(hipStream_t st, int mode, int dtype, const void *x, const void *aux, const int32_t *lengths, void *out,
+                         int B, int Tmax, int D, int n, int ortho, int log_domain, double eps, double n_elems, double *partial,
+                         double *loss) {
+  if (!modspec_fft_takes(n)) {
+    set_error("modspec_batch: the in-LDS FFT takes a power of two in [2, 4096] (got %d)", n);
+    return MLPG_HIP_EINVAL;
+  }
+  int logn = 0;
+  while ((1 << logn) < n) ++logn;
+  BatchArgs p;
+  p.x = x; p.aux = aux; p.lengths = lengths; p.out = out; p.partial = partial;
+  p.B = B; p.T = Tmax; p.D = D; p.n = n; p.logn = logn;
+  p.ortho = ortho; p.log_domain = log_domain;
+  p.eps = eps; p.inv_elems = mode == kBatchLoss ? 1.0 / n_elems : 0.0;
+  if (int rc = dtype == MLPG_HIP_F32 ? launch_batch_typed<float>(st, mode, p) : launch_batch_typed<double>(st, mode, p)) return rc;
+  note_launch(mode == kBatchLoss ? kCountModspecLoss : kCountModspecBatch);
+  if (mode == kBatchLoss) {
+    hipLaunchKernelGGL(modspec_loss_finalize, dim3(1), dim3(256), 0, st, (const double *)partial, B * ((D + 1) / 2), p.inv_elems, loss);
+    MLPG_HIP_CHECK(hipGetLastError());
+  }
+  return 0;
 }
 
 }  // namespace mlpg

@@ -14,6 +14,9 @@
   ms  : modspec_smoothing / modspec (n = 4096) of a config-2 sized trajectory batch 256 x 1000 x 60, float64
   c5  : Merlin-style acoustic paramgen mgc(60)+lf0(1)+bap(5), T=2000, B=512 (1 GPU share of config 5), float64;
         per-stream dense tensors, and the three streams in place from one (B, T, 198) batch (forward_streams)
+  msb : (only with --only msb) forward + backward of the log-MS loss over a padded 256 x 1000 x 60 minibatch, lengths in
+        [600, 1000], float32 and float64, n = 2048 and 4096: (a) a Python loop of autograd.modspec + torch ops, (b)
+        autograd.modspec_batch + torch ops, (c) the fused autograd.modspec_mse_loss
   c5b : (only with --only c5b) forward + backward of the same (512, 2000, 198) batch with gradients for means and variances:
         autograd.multi_stream_mlpg in place against three mlpg_batch on .contiguous() slices plus cat; the epilogue kernel's share
 
@@ -520,6 +523,49 @@ def _run(only, quick, device_index):
             emit(path="c2v-mlpg_batch-step-" + name, ms=ms_s, frames_per_s=B * T / ms_s * 1e3,
                  note="autograd.mlpg_batch forward + backward, requires_grad on means and variances, CHECK_STATUS on")
             del m, v, go, y, mq, vq
+
+    # ---- msb: forward + backward of the log-MS loss over a padded config-2 sized minibatch; only with --only msb ----
+    if args.only and "msb" in args.only.split(","):
+        B, T, D, eps = 256, 1000, 60, 1e-10
+        lengths = np.random.RandomState(1234).randint(600, 1001, size=B)
+        L = torch.from_numpy(lengths.astype(np.int32)).to(dev)
+        live = (torch.arange(T, device=dev)[None, :, None] < L[:, None, None])
+        for name, dt, esz in (("f32", torch.float32, 4), ("f64", torch.float64, 8)):
+            for n in (2048, 4096):
+                nb = n // 2 + 1
+                traj = lambda: (0.1 * torch.cumsum(torch.randn(B, T, D, dtype=torch.float64, device=dev, generator=gen), dim=1) +  # noqa: E731
+                                torch.rand(B, T, D, dtype=torch.float64, device=dev, generator=gen)).to(dt) * live
+                y = traj().requires_grad_()
+                tm = AF.modspec_batch(traj(), n=n, lengths=L).detach()
+                n_elems = float(B * nb * D)
+
+                def loop():             # (a) what the 2-D node allows: one utterance at a time, torch ops for the loss
+                    y.grad = None
+                    total = 0.0
+                    for b in range(B):
+                        ms = AF.modspec(y[b, :lengths[b]], n=n)
+                        total = total + ((torch.log(ms + eps) - torch.log(tm[b] + eps)) ** 2).sum()
+                    (total / n_elems).backward()
+
+                def composed():         # (b) modspec_batch + torch ops
+                    y.grad = None
+                    ms = AF.modspec_batch(y, n=n, lengths=L)
+                    ((torch.log(ms + eps) - torch.log(tm + eps)) ** 2).mean().backward()
+
+                def fused():            # (c) the fused step
+                    y.grad = None
+                    AF.modspec_mse_loss(y, tm, n=n, lengths=L, eps=eps).backward()
+
+                by = float(esz) * B * D * (2 * T + nb)      # (c): y read, target_ms read, grad_x written
+                tag = "%s-n%d" % (name, n)
+                ms_a = gpu_time(loop, steps=3, warmup=1, settle_ms=0)
+                emit(path="msb-loop-2d-node-" + tag, ms=ms_a, note="(a) Python loop of autograd.modspec over %d utterances + torch ops" % B)
+                ms_b = gpu_time(composed, steps=10)
+                emit(path="msb-modspec_batch-torch-" + tag, ms=ms_b, note="(b) autograd.modspec_batch + torch ops for the loss")
+                ms_c = gpu_time(fused, steps=20)
+                emit(path="msb-fused-" + tag, ms=ms_c, alg_bytes=by, GBps=by / ms_c / 1e6, form=_hip.modspec_loss_form(n),
+                     note="(c) autograd.modspec_mse_loss, forward + backward")
+                del y, tm
 
     # ---- c5b: multi-stream MLPG forward + backward at config-5 scale, gradients in place; only with --only c5b ----
     if args.only and "c5b" in args.only.split(","):
