@@ -1,5 +1,7 @@
 // Strip MLPG kernels: dispatch (the kernels live in mlpg_strip_impl.h and are instantiated per
-// dtype in mlpg_strip_{fwd,bwd}_{f32,f64}.hip so that they compile in parallel).
+// dtype in mlpg_strip_{fwd,bwd}_{f32,f64}.hip so that they compile in parallel; the instantiations
+// compiled for the standard window set, which launch_impl picks by the windows' values unless
+// MLPG_STRIP_STDWIN=0, in mlpg_strip_std_{fwd,bwd}_{f32,f64}.hip).
 #include <map>
 #include <mutex>
 #include <utility>

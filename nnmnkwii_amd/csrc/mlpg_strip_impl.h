@@ -648,6 +648,52 @@ __device__ __forceinline__ bool eliminate(double (&Pd)[kM], double (&P1)[kM], do
   return bad;
 }
 
+// ---- the standard window set as compile-time values (STD instantiations) ----
+// static [1], delta [-0.5, 0, 0.5], delta-delta [1, -2, 1]: what nearly every caller passes (a property of the acoustic model).
+// Entries in the order of Args::wc (cm, c0, cp | c00, cpp, cmm, cp0, c0m, cpm), times 4 so that they are integers.  11 of the 27
+// are zero and every other one is +-1 or a power of two, so a kernel that knows them drops the zero terms, adds the unit ones and
+// takes the rest as inline constants (0.25: one scalar pair) -- and needs no coefficient in a scalar register.  Every product with
+// such a coefficient is exact and an fma with it rounds like the add it becomes, so the STD kernels return what the general ones
+// return (a dropped term added +-0: a zero may change its sign, nothing else) -- as long as every precision is finite: the general
+// kernels turn an Inf or NaN precision into NaN accumulators also through 0 * tau, the STD ones test the pivot's refined reciprocal instead (elim_row).
+constexpr int kStd4[3][9] = {{0, 4, 0, 4, 0, 0, 0, 0, 0}, {-2, 0, 2, 0, 1, 1, 0, 0, -1}, {4, -8, 4, 16, 4, 4, -8, -8, 4}};
+enum { qCm, qC0, qCp, qC00, qCpp, qCmm, qCp0, qC0m, qCpm };
+constexpr int std_first(int q) { return kStd4[0][q] ? 0 : (kStd4[1][q] ? 1 : 2); }  // the first window that has entry q
+constexpr bool std_last_has_all() {
+  for (int q = 0; q < 9; ++q)
+    if (kStd4[2][q] == 0) return false;
+  return true;
+}
+static_assert(std_last_has_all(), "every entry has a window that contributes (std_first)");
+// acc (+)= c[w][q] * x.  `init`: the frame's first contribution to acc ASSIGNS it (see assemble_eliminate) -- here the first
+// window whose coefficient is not zero.  w, q, init are constants wherever this is called (unrolled loops): one instruction or none.
+__device__ __forceinline__ void std_term(double &acc, const int w, const int q, const double x, const bool init) {
+  const int c4 = kStd4[w][q];
+  if (c4 == 0) return;
+  if (init && w == std_first(q)) acc = c4 == 4 ? x : (c4 == -4 ? -x : (0.25 * c4) * x);
+  else acc = c4 == 4 ? acc + x : (c4 == -4 ? acc - x : __builtin_fma(0.25 * c4, x, acc));
+}
+// the backward epilogue's tau-free factor c[w][0] x[t-1] + c[w][1] x[t] + c[w][2] x[t+1], rounded as the general kernels' contracted
+// form fma(cp, xp, fma(cm, xm, c0 * x0)) rounds it
+__device__ __forceinline__ double std_apply(const int w, const double xm, const double x0, const double xp) {
+  if (w == 0) return x0;
+  if (w == 1) return __builtin_fma(0.5, xp, -0.5 * xm);
+  return __builtin_fma(-2.0, x0, xm) + xp;
+}
+inline bool std_windows(const WinSet &ws, const double (*wc)[9]) {
+  if (ws.nw != 3 || ws.l[0] != 0 || ws.u[0] != 0 || ws.l[1] != 1 || ws.u[1] != 1 || ws.l[2] != 1 || ws.u[2] != 1) return false;
+  for (int w = 0; w < 3; ++w)
+    for (int q = 0; q < 9; ++q)
+      if (!(wc[w][q] == 0.25 * kStd4[w][q])) return false;
+  return true;
+}
+// MLPG_STRIP_STDWIN=0 (read once per process) keeps every launch on the general instantiations: the A/B switch of
+// profiles/r07_stdwin_notes.md and of tests/test_strip_stdwin_gpu.py, which pins the STD kernels to the general ones.
+inline bool stdwin_enabled() {
+  static const bool on = [] { const char *e = getenv("MLPG_STRIP_STDWIN"); return !(e && *e && atoi(e) == 0); }();
+  return on;
+}
+
 // ---- level 1, streamed: assembly and interior elimination of one chunk in frame order (NW windows, known at
 // compile time) ----
 // The 18 frames f0-1 .. f0+16 are taken one at a time; a frame is NW rows of `var` and of `mean` (one load each per
@@ -664,7 +710,8 @@ struct RingDepth<float> { static constexpr int value = MLPG_STRIP_RING_F32; };  
 // LT (the transposed form with a lengths vector): T is the frame count of the lane group's LONGEST utterance -- what the clamped loads
 // and everything wave-uniform go by -- and Tu this lane's own: its dead frames enter with precision 0 and mean 0 by per-lane
 // SELECTS (their values are padding: anything), its rows >= Tu become identity rows.
-template <typename TIN, bool BWD, int VM, bool EDGE, int NW, bool MULTI = false, bool KEEP = false, bool LT = false>
+// STD: the three standard windows as compile-time coefficients (kStd4; `wc` is not read)
+template <typename TIN, bool BWD, int VM, bool EDGE, int NW, bool MULTI = false, bool KEEP = false, bool LT = false, bool STD = false>
 __device__ __forceinline__ bool assemble_eliminate(__amdgpu_buffer_rsrc_t mrs, __amdgpu_buffer_rsrc_t vrs,
                                                    __amdgpu_buffer_rsrc_t grs, const TIN *__restrict__ vglob,
                                                    unsigned loff, long ldi, long ldg, int sd, int f0, int T, int mw,
@@ -687,7 +734,12 @@ __device__ __forceinline__ bool assemble_eliminate(__amdgpu_buffer_rsrc_t mrs, _
     hi_l[w] = w ? (mw != 0 && Tu - mw > mw ? Tu - mw : mw) : Tu;
     cl[w] = lo[w] < T ? lo[w] : T - 1;            // a window without live frames still loads (frame cl) and weighs 0
     ch[w] = hi[w] > cl[w] ? hi[w] : cl[w] + 1;
-    k[w] = win_coef<TIN, VM>(wc, w, vglob, sd);
+    if (STD) {
+      k[w] = WinCoef{};
+      k[w].tau_glob = VM == MLPG_HIP_VAR_GLOBAL ? tau_of<TIN>(vglob[w * sd]) : 1.0;
+    } else {
+      k[w] = win_coef<TIN, VM>(wc, w, vglob, sd);
+    }
     // unit variances: the precision 1.0 as an opaque per-lane run-time value.  As a literal (or any wave-uniform value)
     // the whole matrix becomes uniform arithmetic that the compiler hoists above the stream and spills (544-880 B/lane).
     if (VM == MLPG_HIP_VAR_UNIT) {
@@ -737,6 +789,36 @@ __device__ __forceinline__ bool assemble_eliminate(__amdgpu_buffer_rsrc_t mrs, _
       if (KEEP && i < kM) tk[i + 1][w] = (float)tau;  // float32 inputs: exact (a float32 reciprocal, or 0); float64 inputs: rounded
       double tm = 0.0;
       if (!BWD) tm = tau * mval;
+      if (STD) {
+        static_assert(!STD || NW == 3, "the standard set has three windows");
+        // the general form below without its zero terms (std_term).  tm as an opaque value where it is added with coefficient +-1
+        // (windows 0 and 2): the product must be rounded first, as the general kernels round it, not contracted into that add
+        if (!BWD && w != 1) asm("" : "+v"(tm));
+        if (i >= 0 && i < kM) {  // row t
+          std_term(Pd[i], w, qC00, tau, false);
+          std_term(P1[i], w, qCp0, tau, true);
+          if (!BWD) std_term(rhs[i], w, qC0, tm, false);
+        }
+        if (i + 1 >= 0 && i + 1 < kM) {  // row t+1
+          std_term(Pd[i + 1], w, qCpp, tau, true);
+          if (!BWD) std_term(rhs[i + 1], w, qCp, tm, true);
+        }
+        if (i - 1 >= 0 && i - 1 < kM) {  // row t-1
+          std_term(Pd[i - 1], w, qCmm, tau, false);
+          std_term(P1[i - 1], w, qC0m, tau, false);
+          std_term(P2[i - 1], w, qCpm, tau, true);
+          if (!BWD) std_term(rhs[i - 1], w, qCm, tm, false);
+        }
+        if (i == -1) {
+          std_term(ca, w, qCpm, tau, true);
+          std_term(cb, w, qCp0, tau, true);
+        }
+        if (i == 0) {
+          std_term(cb, w, qC0m, tau, false);
+          std_term(cc, w, qCpm, tau, true);
+        }
+        continue;
+      }
       const bool first = w == 0;  // first contribution to: Pd, rhs of row t+1; P1 of row t; P2 of row t-1
       if (i >= 0 && i < kM) {  // row t
         Pd[i] += k[w].c00 * tau;
@@ -804,10 +886,19 @@ __device__ __forceinline__ bool assemble_eliminate(__amdgpu_buffer_rsrc_t mrs, _
       }
     }
     const double dd = Pd[i];
-    bad |= !(dd > 0.0);
     const double dinv = fast_rcp(dd);
+    // STD: the pivot must be positive AND finite.  An Inf precision, which the general kernels meet as 0 * Inf = NaN in one of their
+    // zero terms, arrives here as a pivot of +Inf; its reciprocal as fast_rcp refines it is NaN (as it is for 0 and NaN, and negative
+    // for a negative pivot), so the test is made on the reciprocal -- one compare as before.  (v_cmp_class_f64 would need its mask,
+    // which is no inline constant, in a register for the whole kernel: two VGPRs more than the general instance.)
+    if (STD) bad |= !(dinv > 0.0);
+    else bad |= !(dd > 0.0);
     const double e1 = P1[i], e2 = P2[i];
     const double l1 = e1 * dinv, l2 = e2 * dinv;
+    // STD: P1[i + 1] is so far one product, -2 * tau of the frame just accumulated (every other accumulator that is updated here has
+    // had an add since its assignment).  As an opaque value, so that P1[i + 1] - l2 * e1 contracts as in the general kernels, to
+    // fma(-l2, e1, P1[i + 1]): left the choice, the compiler fuses the exact product and rounds l2 * e1 on its own instead.
+    if (STD && i + 1 < kM) asm("" : "+v"(P1[i + 1]));
     Pd[i + 1] -= l1 * e1;
     P1[i + 1] -= l2 * e1;
     Pd[i + 2] -= l2 * e2;
@@ -913,9 +1004,13 @@ __device__ __forceinline__ void backsub(const double (&Pd)[kM], const double (&P
 // counts is compiled into the kernel (round 5: those forms alone cost the backward instances ~280 spilled scalar
 // registers and 20 k instructions of code); NW3 = false serves one, two or more than three windows.
 // TR (MULTI kernels): the lanes of a group run over several utterances of one narrow stream (StreamMap::tr_u).
-template <typename TIN, typename TOUT, bool BWD, int VM, bool MULTI = false, bool NW3 = true, bool TR = false>
+// STD: the launch has the STANDARD three windows (std_windows(): launch_impl checked the values): level 1 and the backward epilogue
+// are compiled for those coefficients (kStd4) -- no coefficient is fetched from the argument segment or held in a scalar register,
+// the 11 of 27 terms per frame that multiply by zero do not exist (profiles/r07_stdwin_notes.md).  Everything else is the same code.
+template <typename TIN, typename TOUT, bool BWD, int VM, bool MULTI = false, bool NW3 = true, bool TR = false, bool STD = false>
 __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem p, WinSet ws, Args a) {
   static_assert(!TR || MULTI, "the transposed form is a MULTI kernel");
+  static_assert(!STD || (NW3 && !MULTI), "the standard-window form: three windows, one stream");
   extern __shared__ __align__(16) unsigned char smem[];
   double *lds_rec = (double *)smem;                                  // [kW][kRec][64]   (level 1 -> 2)
   double *lds_stage = (double *)smem;                                // [kStage][kRec][64] (level 3), same bytes
@@ -1071,7 +1166,7 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
       // the usual three windows: assembly and elimination streamed in frame order
       double wcl[3][9];
       const double (*wcs)[9] = a.wc;
-      if (BWD && MLPG_STRIP_BWD_KARG) {
+      if (!STD && BWD && MLPG_STRIP_BWD_KARG) {
         // the six coefficient products per window the backward stream uses (entries 3 .. 8), fetched here
         double c6[3][6];
         karg_f64x6<kKargWc + 0 * 72 + 24>(c6[0]);
@@ -1085,14 +1180,14 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
         }
         wcs = wcl;
       }
-      if (!BWD && MLPG_STRIP_FWD_KARG && !MULTI) {
+      if (!STD && !BWD && MLPG_STRIP_FWD_KARG && !MULTI) {
         karg_f64x9<kKargWc + 0 * 72>(wcl[0]);
         karg_f64x9<kKargWc + 1 * 72>(wcl[1]);
         karg_f64x9<kKargWc + 2 * 72>(wcl[2]);
         wcs = wcl;
       }
-      if (interior) bad = assemble_eliminate<TIN, BWD, VM, false, 3, MULTI, kKeepTau>(mrs, vrs, grs, vglob, loff, ldi, ldg, sd, f0, T, mw, wcs, a.one, Pd, P1, P2, rhs, ca, cb, cc, rec, tk);
-      else bad = assemble_eliminate<TIN, BWD, VM, true, 3, MULTI, kKeepTau, TR>(mrs, vrs, grs, vglob, loff, ldi, ldg, sd, f0, T, mw, wcs, a.one, Pd, P1, P2, rhs, ca, cb, cc, rec, tk, Tu);
+      if (interior) bad = assemble_eliminate<TIN, BWD, VM, false, 3, MULTI, kKeepTau, false, STD>(mrs, vrs, grs, vglob, loff, ldi, ldg, sd, f0, T, mw, wcs, a.one, Pd, P1, P2, rhs, ca, cb, cc, rec, tk);
+      else bad = assemble_eliminate<TIN, BWD, VM, true, 3, MULTI, kKeepTau, TR, STD>(mrs, vrs, grs, vglob, loff, ldi, ldg, sd, f0, T, mw, wcs, a.one, Pd, P1, P2, rhs, ca, cb, cc, rec, tk, Tu);
       STRIP_TICK(1);
 #ifdef MLPG_STRIP_TRACE
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1263,8 +1358,10 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
       const unsigned ooff_e = (unsigned)d * (unsigned)sizeof(TOUT);
       (void)ors_e; (void)ooff_e;
       // the three coefficients per window (entries 0 .. 2 of wc[w]), fetched here (see karg_f64x6)
-      double we[3][3];
-      if (MLPG_STRIP_BWD_KARG) {
+      double we[3][3] = {};
+      if (STD) {
+        // (std_apply: no coefficient)
+      } else if (MLPG_STRIP_BWD_KARG) {
         karg_f64x3<kKargWc + 0 * 72>(we[0]);
         karg_f64x3<kKargWc + 1 * 72>(we[1]);
         karg_f64x3<kKargWc + 2 * 72>(we[2]);
@@ -1311,7 +1408,7 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
             tau = (double)tf;
           }
           else if (lv) tau = VM == MLPG_HIP_VAR_FRAME ? tau_of<TIN>(tv[sl][w]) : tg[w];
-          const double gval = tau * (we[w][0] * xm + we[w][1] * x0 + we[w][2] * xp);
+          const double gval = STD ? tau * std_apply(w, xm, x0, xp) : tau * (we[w][0] * xm + we[w][1] * x0 + we[w][2] * xp);
           put(w, zero_out ? (TOUT)0 : (TOUT)gval);
         }
       };
@@ -1914,6 +2011,23 @@ inline int resident_grid(const void *kern, int threads, size_t lds, int *out) {
   return 0;
 }
 
+// The STD instantiations (per-frame variances, forward and backward) are compiled in translation units of their own,
+// mlpg_strip_std_*.hip, so that the build stays parallel: std_kernel() hands out their entry points.
+// Not among them: backward with float64 gradients in AND out.  The general instance sits at 248 VGPRs there and the STD one tips
+// over into scratch (256 VGPRs, 56 bytes: profiles/r07_stdwin_notes.md section 2), so that pair stays with the general kernel.
+template <typename TIN, typename TOUT, bool BWD>
+constexpr bool kHasStd = !(BWD && sizeof(TIN) == 8 && sizeof(TOUT) == 8);
+typedef void (*KernelFn)(Problem, WinSet, Args);
+template <typename TIN, typename TOUT, bool BWD>
+KernelFn std_kernel();
+template <> KernelFn std_kernel<double, double, false>();
+template <> KernelFn std_kernel<float, float, false>();
+template <> KernelFn std_kernel<double, float, true>();
+template <> KernelFn std_kernel<float, float, true>();
+template <> KernelFn std_kernel<float, double, true>();
+#define MLPG_STRIP_STD_KERNEL(TIN, TOUT, BWD) \
+  template <> KernelFn std_kernel<TIN, TOUT, BWD>() { return strip_kernel<TIN, TOUT, BWD, MLPG_HIP_VAR_FRAME, false, true, false, true>; }
+
 template <typename TIN, typename TOUT, bool BWD, bool MULTI, bool TR = false>
 int launch_impl(hipStream_t st, const Problem &p, const WinSet &ws, void *scratch_base, int R, int ndg, int dgw,
                 bool zero_ctrl, const StreamMap *smap) {
@@ -2006,6 +2120,10 @@ int launch_impl(hipStream_t st, const Problem &p, const WinSet &ws, void *scratc
     return go(strip_kernel<TIN, TOUT, false, MLPG_HIP_VAR_FRAME, true, true, TR>);
   } else {
     if (ws.nw == 3) {
+      // the standard windows with per-frame variances: the instantiation compiled for them (same kernel family, same count)
+      if constexpr (kHasStd<TIN, TOUT, BWD>) {
+        if (p.var_mode == MLPG_HIP_VAR_FRAME && std_windows(ws, a.wc) && stdwin_enabled()) return go(std_kernel<TIN, TOUT, BWD>());
+      }
       switch (p.var_mode) {
         case MLPG_HIP_VAR_FRAME: return go(strip_kernel<TIN, TOUT, BWD, MLPG_HIP_VAR_FRAME, false, true>);
         case MLPG_HIP_VAR_GLOBAL: return go(strip_kernel<TIN, TOUT, BWD, MLPG_HIP_VAR_GLOBAL, false, true>);

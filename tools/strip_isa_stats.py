@@ -1,0 +1,179 @@
+#!/usr/bin/env python
+"""Static ISA statistics of the strip kernels (needs hipcc, no GPU).
+
+Compiles strip translation units of nnmnkwii_amd/csrc for gfx950 with the build's own flags, device side only, to
+assembly (--cuda-device-only -S) and prints per kernel: VGPRs, scalar registers, spilled scalar registers, scratch bytes
+and instruction counts by class.  What it is for: a change to the strip kernel's level 1 is judged by the instructions a
+wavefront executes (profiles/r06_notes.md section 3), and the register figures decide whether two workgroups still fit
+a CU (<= 256 VGPRs, no scratch).
+
+    python tools/strip_isa_stats.py                      # forward float64: general and standard-window units
+    python tools/strip_isa_stats.py mlpg_strip_bwd_f32.hip mlpg_strip_std_bwd_f32.hip
+    python tools/strip_isa_stats.py --json ...
+
+tests/test_strip_isa_stats.py pins the standard-window forward-float64 instance against the general one with it.
+"""
+import argparse
+import json
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "nnmnkwii_amd", "csrc")
+DEFAULT = ["mlpg_strip_fwd_f64.hip", "mlpg_strip_std_fwd_f64.hip"]
+
+_F64_ARITH = re.compile(r"^v_(add|mul|fma|fmac)_f64")
+_KERNEL_ARGS = re.compile(r"strip_kernelI(.*?)EEvNS_7ProblemE")
+
+
+def find_hipcc():
+    for c in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", shutil.which("hipcc")):
+        if c and os.path.exists(c):
+            return c
+    return None
+
+
+def _flags(src):
+    sys.path.insert(0, ROOT)
+    try:
+        from nnmnkwii_amd.csrc import build as B
+    finally:
+        sys.path.pop(0)
+    return [*B.FLAGS, *B.FILE_FLAGS.get(src, ["-ffp-contract=fast"]), *B.EXTRA]
+
+
+def assembly(src, hipcc=None):
+    """The device-side assembly text of one translation unit of csrc/."""
+    hipcc = hipcc or find_hipcc()
+    if hipcc is None:
+        raise RuntimeError("hipcc not found")
+    cmd = [hipcc, "-x", "hip", *_flags(src), "--cuda-device-only", "-S", os.path.join(CSRC, src), "-o", "-"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("hipcc failed:\n%s\n%s" % (" ".join(cmd), r.stderr[-4000:]))
+    return r.stdout
+
+
+def _classify(op):
+    if op.startswith("v_readlane") or op.startswith("v_writelane"):
+        return op.split("_b32")[0]
+    if op.startswith("v_"):
+        return "valu"
+    if op.startswith(("s_load", "s_buffer_load")):
+        return "smem"
+    if op.startswith("s_waitcnt"):
+        return "waitcnt"
+    if op.startswith("s_"):
+        return "salu"
+    if op.startswith("ds_"):
+        return "lds"
+    if op.startswith(("buffer_", "global_", "flat_", "scratch_")):
+        return "vmem"
+    return "other"
+
+
+def template_args(mangled):
+    """strip_kernel's template arguments as they are mangled, e.g. ['d', 'd', 'Lb0E', 'Li0E', 'Lb0E', 'Lb1E', 'Lb0E', 'Lb1E']
+    = <TIN, TOUT, BWD, VM, MULTI, NW3, TR, STD>; None for other kernels."""
+    m = _KERNEL_ARGS.search(mangled)
+    if not m:
+        return None
+    return re.findall(r"L[bi]\d+E|[df]", m.group(1) + "E")
+
+
+def parse(asm):
+    """{mangled kernel name: stats} for every kernel of an assembly text."""
+    out = {}
+    cur = None
+    for line in asm.splitlines():
+        t = line.strip()
+        m = re.match(r"\.type\s+(\S+),@function", t)
+        if m:
+            cur = {"mangled": m.group(1), "instructions": 0, "valu": 0, "f64_arith": 0, "v_readlane": 0, "v_writelane": 0, "salu": 0,
+                   "smem": 0, "waitcnt": 0, "lds": 0, "vmem": 0, "other": 0}
+            continue
+        if cur is None:
+            continue
+        if t.startswith(".Lfunc_end"):
+            out[cur["mangled"]] = cur
+            cur["_closed"] = True
+            continue
+        if cur.get("_closed"):
+            for key, pat in (("sgprs", r"; TotalNumSgprs: (\d+)"), ("vgprs", r"; NumVgprs: (\d+)"), ("agprs", r"; NumAgprs: (\d+)"),
+                             ("scratch_bytes", r"; ScratchSize: (\d+)"), ("occupancy", r"; Occupancy: (\d+)"),
+                             ("code_bytes", r"; codeLenInByte = (\d+)")):
+                mm = re.match(pat, t)
+                if mm:
+                    cur[key] = int(mm.group(1))
+            continue
+        if not t or t[0] in ".;" or t.endswith(":") or t.startswith("//"):
+            continue
+        op = t.split()[0]
+        if not re.match(r"^[a-z][a-z0-9_]*$", op):
+            continue
+        cur["instructions"] += 1
+        cur[_classify(op)] += 1
+        if op.startswith(("v_readlane", "v_writelane")):
+            cur["valu"] += 1  # lane moves of spilled scalar registers are vector instructions too
+        if _F64_ARITH.match(op):
+            cur["f64_arith"] += 1
+    # spilled scalar registers: from the code object's metadata (one document per unit, kernels by .name)
+    name = None
+    for line in asm.splitlines():
+        t = line.strip()
+        m = re.match(r"-?\s*\.name:\s+(\S+)", t)
+        if m:
+            name = m.group(1)
+        m = re.match(r"\.sgpr_spill_count:\s+(\d+)", t)
+        if m and name in out:
+            out[name]["sgpr_spills"] = int(m.group(1))
+        m = re.match(r"\.vgpr_spill_count:\s+(\d+)", t)
+        if m and name in out:
+            out[name]["vgpr_spills"] = int(m.group(1))
+    for st in out.values():
+        st.pop("_closed", None)
+    return out
+
+
+def stats(src, hipcc=None):
+    return parse(assembly(src, hipcc))
+
+
+def _label(mangled):
+    a = template_args(mangled)
+    if a is None:
+        return mangled[:60]
+    names = ("TIN", "TOUT", "BWD", "VM", "MULTI", "NW3", "TR", "STD")
+    val = lambda x: {"d": "f64", "f": "f32"}.get(x, x[2:-1])
+    return "strip_kernel<" + ", ".join("%s=%s" % (n, val(x)) for n, x in zip(names, a)) + ">"
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("sources", nargs="*", default=DEFAULT, help="translation units of nnmnkwii_amd/csrc (default: %s)" % " ".join(DEFAULT))
+    ap.add_argument("--json", action="store_true", help="one JSON object instead of the table")
+    ap.add_argument("--all", action="store_true", help="every kernel of the unit, not only strip_kernel instances")
+    args = ap.parse_args()
+    if find_hipcc() is None:
+        print("hipcc not found", file=sys.stderr)
+        return 2
+    res = {}
+    for src in args.sources:
+        res[src] = {k: v for k, v in stats(os.path.basename(src)).items() if args.all or template_args(k) is not None}
+    if args.json:
+        print(json.dumps(res, indent=1, sort_keys=True))
+        return 0
+    cols = ("vgprs", "sgpr_spills", "scratch_bytes", "instructions", "valu", "f64_arith", "v_readlane", "v_writelane", "salu", "smem", "waitcnt", "vmem", "lds")
+    for src, ks in res.items():
+        print(src)
+        for k, st in ks.items():
+            print("  " + _label(k))
+            print("    " + "  ".join("%s=%s" % (c, st.get(c, "?")) for c in cols))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
