@@ -83,7 +83,8 @@ const char *mlpg_hip_last_error(void);
  * host-memory calls (mlpg_hip_forward_host_multi / mlpg_hip_fastdtw_host_multi) have enqueued on device d; 13 launches of the
  * variance-gradient kernel of mlpg_hip_backward_var; 15 launches of the stream-table epilogue of mlpg_hip_backward_streams; 17
  * launches of the typed in-LDS FFT kernel of mlpg_hip_modspec_batch / mlpg_hip_modspec_batch_backward, 18 transforms those two
- * calls sent through the direct transform, 19 launches of the fused loss kernel of mlpg_hip_modspec_loss_step; -1 for
+ * calls sent through the direct transform, 19 launches of the fused loss kernel of mlpg_hip_modspec_loss_step; 20 CALLS of
+ * mlpg_hip_modspec / _inv_modspec / _modspec_smoothing / _modspec_backward that the chirp-z kernel served (one per call); -1 for
  * any other `kind` (12, 14 and 16 included).
  * (Tests use it to assert WHICH kernel / route a call took.) */
 long long mlpg_hip_launch_count(int kind);
@@ -424,8 +425,17 @@ int mlpg_hip_delta_features(int device, void *stream, int dtype, const void *x,
  * Any DFT length n >= 2, as numpy's rfft / irfft.  A power of two <= 4096 (the
  * reference's defaults are 2048 and 4096): one workgroup per (utterance, pair of
  * feature columns), the n-point FFT lives in LDS, one launch per call.  Any
- * other n: the direct transform (O(n) per output value, exact integer phases;
- * two launches for smoothing / backward, the half spectrum in stream scratch).
+ * other n <= 2048: the chirp-z (Bluestein) transform on the same FFT at length
+ * M = 2^ceil(log2(2n - 1)) <= 4096, the same workgroup shape, two M-point FFTs
+ * per workgroup (four for smoothing / backward); two small launches in front
+ * build its tables (n + M complex values) in stream scratch on every call.
+ * Every other n (no power of two above 2048, or n > 4096): the direct transform
+ * (O(n) per output value, exact integer phases; two launches for smoothing /
+ * backward, the half spectrum in stream scratch).
+ * mlpg_hip_modspec_route(n): the route these four calls take at length n, a
+ * function of n and of mlpg_hip_modspec_set_direct's switch alone -- 0 FFT,
+ * 1 direct, 2 chirp-z, -1 for n < 2 (refused).  mlpg_hip_launch_count(20) counts
+ * the calls the chirp-z route served.
  * All arrays float64, row-major; `ortho` selects numpy's norm="ortho".
  *   x     : (B, T, D), T <= n, zero-padded to n internally
  *   ms    : (B, n/2+1, D)            phase : (B, n/2+1, D, 2) (re, im), may be NULL
@@ -445,8 +455,9 @@ int mlpg_hip_modspec_backward(int device, void *stream, const double *x,
                               const double *grad_ms, int B, int T, int D,
                               int n, int ortho, double *grad_x);
 /* Testing aid: on != 0 routes every DFT length through the direct transform
- * (process-wide), so that tests can compare it with the FFT path. */
+ * (process-wide), so that tests can compare it with the FFT and chirp-z paths. */
 void mlpg_hip_modspec_set_direct(int on);
+int mlpg_hip_modspec_route(int n);
 
 /*
  * The modulation spectrum over a PADDED MINIBATCH, float32 or float64, and the fused log-MS loss step -- what follows the

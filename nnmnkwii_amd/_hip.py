@@ -40,6 +40,7 @@ EXPORTS = (
     "mlpg_hip_modspec_smoothing",
     "mlpg_hip_modspec_backward",
     "mlpg_hip_modspec_set_direct",
+    "mlpg_hip_modspec_route",
     "mlpg_hip_modspec_batch",
     "mlpg_hip_modspec_batch_backward",
     "mlpg_hip_modspec_loss_form",
@@ -170,6 +171,8 @@ def lib():
         L.mlpg_hip_modspec_backward.argtypes = [ci, vp, vp, vp, ci, ci, ci, ci, ci, vp]
         L.mlpg_hip_modspec_set_direct.restype = None
         L.mlpg_hip_modspec_set_direct.argtypes = [ci]
+        L.mlpg_hip_modspec_route.restype = ci
+        L.mlpg_hip_modspec_route.argtypes = [ci]
         L.mlpg_hip_modspec_batch.restype = ci
         L.mlpg_hip_modspec_batch.argtypes = [ci, vp, ci, vp, vp, ci, ci, ci, ci, ci, vp]
         L.mlpg_hip_modspec_batch_backward.restype = ci
@@ -772,6 +775,12 @@ def modspec_backward(x, grad_ms, n, ortho=False):
     _check(lib().mlpg_hip_modspec_backward(x.device.index, _stream(x.device), _p(x), _p(g), B, T, D, int(n), int(bool(ortho)),
                                            _p(out)), "mlpg_hip_modspec_backward")
     return out
+
+
+def modspec_route(n):
+    """mlpg_hip_modspec_route: the route modspec / inv_modspec / modspec_smoothing / modspec_backward take at DFT length n -- 0 the
+    in-LDS FFT, 1 the direct transform, 2 chirp-z, -1 for n < 2 (the library's own decision, not a copy of it)."""
+    return int(lib().mlpg_hip_modspec_route(int(n)))
 
 
 def _batch_args(x, lengths):

@@ -553,6 +553,15 @@ __attribute__((visibility("default"))) int mlpg_hip_delta_features(int device, v
 }
 
 namespace {
+// The route of the float64 entries, by the DFT length and the direct switch alone (mlpg_hip_modspec_route): 0 the in-LDS FFT,
+// 1 the direct transform, 2 chirp-z, -1 no transform (n < 2)
+int modspec_route(int n) {
+  if (n < 2) return -1;
+  if (g_modspec_direct) return 1;
+  if (modspec_fft_takes(n)) return 0;
+  return modspec_chirp_takes(n) ? 2 : 1;
+}
+
 int modspec_entry(int device, void *stream, int mode, const double *x, const double *ms, const double *ph, double *out,
                   double *out_ph, int B, int T, int D, int n, int ortho, int limit_bin, int log_domain) {
   if (B < 0 || T < 0 || D < 0 || n < 1) {
@@ -572,19 +581,30 @@ int modspec_entry(int device, void *stream, int mode, const double *x, const dou
     set_error("modspec: NULL pointer");
     return MLPG_HIP_EINVAL;
   }
+  if (int rc = check_device("modspec", device)) return rc;  // (as the padded-minibatch entries: asked before the runtime is touched)
   DeviceGuard g("modspec", device);
   if (g.rc) return g.rc;
-  // powers of two up to 4096 (the reference's defaults are 2048 and 4096): the fused in-LDS FFT; any other length:
-  // the direct transform of modspec_dft.hip
-  if (n <= 4096 && !(n & (n - 1)) && !g_modspec_direct)
-    return launch_modspec((hipStream_t)stream, mode, x, ms, ph, out, out_ph, B, T, D, n, ortho, limit_bin, log_domain);
-  return launch_modspec_dft((hipStream_t)stream, device, mode, x, ms, ph, out, out_ph, B, T, D, n, ortho, limit_bin,
-                            log_domain);
+  const hipStream_t st = (hipStream_t)stream;
+  switch (modspec_route(n)) {
+    case 0:  // powers of two up to 4096 (the reference's defaults are 2048 and 4096): the fused in-LDS FFT
+      return launch_modspec(st, mode, x, ms, ph, out, out_ph, B, T, D, n, ortho, limit_bin, log_domain);
+    case 2: {  // any other length up to 2048: the chirp-z transform on that FFT
+      const int rc = launch_modspec_chirp(st, device, mode, x, ms, ph, out, out_ph, B, T, D, n, ortho, limit_bin, log_domain);
+      if (rc == 0) note_launch(kCountModspecChirp);
+      return rc;
+    }
+  }
+  // the rest, and every length behind mlpg_hip_modspec_set_direct(1): the direct transform of modspec_dft.hip
+  return launch_modspec_dft(st, device, mode, x, ms, ph, out, out_ph, B, T, D, n, ortho, limit_bin, log_domain);
 }
 }  // namespace
 
 // Testing aid: route every DFT length through the direct transform (so that it can be compared with the FFT path).
 __attribute__((visibility("default"))) void mlpg_hip_modspec_set_direct(int on) { g_modspec_direct = on != 0; }
+
+// The route mlpg_hip_modspec, _inv_modspec, _modspec_smoothing and _modspec_backward take at DFT length n (modspec_entry decides
+// with this very function).
+__attribute__((visibility("default"))) int mlpg_hip_modspec_route(int n) { return modspec_route(n); }
 
 __attribute__((visibility("default"))) int mlpg_hip_modspec(int device, void *stream, const double *x, int B, int T,
                                                             int D, int n, int ortho, double *ms, double *phase) {

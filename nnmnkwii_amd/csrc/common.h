@@ -134,8 +134,9 @@ SideStreams *side_streams(int device);
 // launches per kernel family since the library was loaded (mlpg_hip_launch_count: a test aid)
 // (kinds 12 and 14 count nothing and read -1; 13: the variance-gradient epilogue of mlpg_hip_backward_var; 15: the stream-table
 // epilogue of mlpg_hip_backward_streams; 16 counts nothing and reads -1; 17: the typed in-LDS FFT kernel of mlpg_hip_modspec_batch /
-// _batch_backward; 18: their direct transform; 19: the fused loss kernel of mlpg_hip_modspec_loss_step)
-enum { kCountGeneric = 0, kCountWave, kCountStrip, kCountStripMulti, kCountConst, kCountFused, kCountChunk, kCountFir, kCountConstMulti, kCountStripTr, kCountHostSmall, kCountHostSmallDirect, kCountUnused12, kCountVarGrad, kCountUnused14, kCountStreamsBwd, kCountUnused16, kCountModspecBatch, kCountModspecBatchDft, kCountModspecLoss, kCountKinds };
+// _batch_backward; 18: their direct transform; 19: the fused loss kernel of mlpg_hip_modspec_loss_step; 20: calls of the float64 modulation-spectrum entries that
+// the chirp-z kernel of modspec_chirp.hip served)
+enum { kCountGeneric = 0, kCountWave, kCountStrip, kCountStripMulti, kCountConst, kCountFused, kCountChunk, kCountFir, kCountConstMulti, kCountStripTr, kCountHostSmall, kCountHostSmallDirect, kCountUnused12, kCountVarGrad, kCountUnused14, kCountStreamsBwd, kCountUnused16, kCountModspecBatch, kCountModspecBatchDft, kCountModspecLoss, kCountModspecChirp, kCountKinds };
 void note_launch(int kind);
 // Grow-only scratch, cached per (device, stream, slot): slot 0 generic factor, 1 fastdtw pyramids,
 // 2 generic status, 3 strip records, 4 constant-coefficient kernel (factor table), 5 fastdtw from host costs (D rows, back-pointers), 6 chunked kernel (records, block factors, separator solutions, marks).  Returns nullptr (and sets the error) on failure.
@@ -200,6 +201,12 @@ void host_api_shutdown();  // host_api.hip: streams, events, pinned and device s
 int launch_modspec_dft(hipStream_t s, int device, int mode, const double *x, const double *ms, const double *ph,
                        double *out, double *out_ph, int B, int T, int D, int n, int ortho, int limit_bin,
                        int log_domain);
+// modspec_chirp.hip: the same four modes at a DFT length in [3, 2048] that is no power of two (chirp-z on the in-LDS FFT; the two
+// tables go to scratch slot 0 of the stream)
+bool modspec_chirp_takes(int n);
+int modspec_chirp_length(int n);  // M = 2^ceil(log2(2n - 1)), the length of its circular convolution
+int launch_modspec_chirp(hipStream_t s, int device, int mode, const double *x, const double *ms, const double *ph, double *out,
+                         double *out_ph, int B, int T, int D, int n, int ortho, int limit_bin, int log_domain);
 // padded minibatches, float32 / float64 (modspec_api.hip): mode 0 spectrum, 1 gradient (aux: grad_ms), 2 -- FFT form only -- the fused
 // loss step (aux: target_ms; partial: one double per workgroup, B * ceil(D / 2); loss: one double)
 bool modspec_fft_takes(int n);  // a power of two in [2, 4096]: the in-LDS FFT

@@ -7,9 +7,16 @@ of the LDS-resident FFT kernels behind ``include/mlpg_hip.h`` (``mlpg_hip_modspe
 ``(B, T, D)`` batch is accepted wherever the reference takes ``(T, D)``.
 
 Arithmetic is float64 on the device; results are cast to what numpy would return for the input
-dtype (float32 in -> float32 / complex64 out).  DFT lengths must be powers of two up to 4096
-(the reference's defaults and tests; anything else raises ``NotImplementedError`` -- there is no
-CPU fallback).
+dtype (float32 in -> float32 / complex64 out).  Every DFT length ``n >= 2`` is taken, as numpy's
+rfft / irfft take it, on one of three routes chosen by ``n`` alone (``_hip.modspec_route(n)``):
+
+* a power of two up to 4096 (the reference's defaults and tests): the in-LDS FFT;
+* any other ``n`` up to 2048: the chirp-z (Bluestein) transform on that FFT at length
+  ``2^ceil(log2(2n - 1))``, the same one workgroup per utterance and pair of columns;
+* everything else (no power of two above 2048, or ``n > 4096``): the direct O(n^2) transform.
+
+For an odd ``n``, ``modspec_smoothing`` inverts at ``n - 1`` as the reference does; each of its two
+legs takes the route of its own length.  There is no CPU fallback.
 """
 import numpy as np
 
