@@ -599,6 +599,47 @@ int mlpg_hip_gmm_convert(int device, void *stream, const double *x,
                          double *out);
 
 /*
+ * Float64 EM for full-covariance Gaussian mixtures on the device (K6, csrc/gmm_em.hip): scikit-learn's _e_step / _m_step
+ * (sklearn/mixture/_base.py, _gaussian_mixture.py) restated step by step.  Limits: 1 <= F <= 128 features, 1 <= K <= 64
+ * components, N >= 0 rows; all arrays float64, row-major, on the device.  Every argument is checked before a device is
+ * selected; N == 0 returns 0 and touches nothing.  No floating-point atomics: two calls on the same inputs give the same bits.
+ *
+ * mlpg_hip_gmm_workspace_bytes: the workspace one fit of this shape needs (partial sums of the E-step's mean and of the
+ * M-step's row slices; their number depends on (N, F, K) alone).  0 for sizes outside the limits.
+ *
+ * mlpg_hip_gmm_estep: X (N, F), weights (K), means (K, F), prec_chol (K, F, F) upper factors U with U U^T = Sigma^-1,
+ * log_det (K) = sum_i log U_ii.  log p_nk = -(F log 2 pi + |(x_n - mu_k) U_k|^2) / 2 + log_det_k; with the log weights added,
+ * log_prob_norm_n is their log-sum-exp over k and resp_nk = exp(log p_nk + log w_k - log_prob_norm_n).  Every output may be
+ * NULL: resp (N, K), log_prob_norm (N), labels int32 (N) (the arg-max component, the first of equals), mean_log_prob (one
+ * double: the mean of log_prob_norm; needs the workspace, which is not read otherwise).
+ *
+ * mlpg_hip_gmm_mstep: nk = sum_n resp_nk + 10 eps, means = sum_n resp_nk x_n / nk, covariances_k = sum_n resp_nk (x_n - mu_k)
+ * (x_n - mu_k)^T / nk + reg_covar I with the new means, weights = nk / sum_k nk.  Outputs weights (K), means (K, F),
+ * covariances (K, F, F) (exactly symmetric).
+ *
+ * mlpg_hip_gmm_precisions: per component the Cholesky factor L of the covariance, prec_chol = L^-T (exact zeros below the
+ * diagonal), log_det, and status int32 (K): 0, or the 1-based index of a pivot that is <= 0 or NaN (LAPACK dpotrf's rule;
+ * prec_chol and log_det of that component are then not written).
+ */
+size_t mlpg_hip_gmm_workspace_bytes(int64_t N, int F, int K);
+int mlpg_hip_gmm_estep(int device, void *stream, const double *X,
+                       const double *weights, const double *means,
+                       const double *prec_chol, const double *log_det,
+                       int64_t N, int F, int K, double *resp,
+                       double *log_prob_norm, int32_t *labels,
+                       double *mean_log_prob, void *workspace,
+                       size_t workspace_bytes);
+int mlpg_hip_gmm_mstep(int device, void *stream, const double *X,
+                       const double *resp, int64_t N, int F, int K,
+                       double reg_covar, double *weights, double *means,
+                       double *covariances, void *workspace,
+                       size_t workspace_bytes);
+int mlpg_hip_gmm_precisions(int device, void *stream,
+                            const double *covariances, int F, int K,
+                            double *prec_chol, double *log_det,
+                            int32_t *status);
+
+/*
  * Gather rows along the warping path into zero-padded outputs.  Replaces
  * alignment.py:52-54,72-73:  out[n, k, :] = src[n, path[n, k], :] for
  * k < path_len[n], zeros after.  src (N, Tsrc, D), out (N, Tout, D), same dtype.

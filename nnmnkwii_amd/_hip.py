@@ -65,6 +65,10 @@ EXPORTS = (
     "mlpg_hip_backward_host",
     "mlpg_hip_backward_var",
     "mlpg_hip_backward_streams",
+    "mlpg_hip_gmm_workspace_bytes",
+    "mlpg_hip_gmm_estep",
+    "mlpg_hip_gmm_mstep",
+    "mlpg_hip_gmm_precisions",
 )
 
 
@@ -209,6 +213,14 @@ def lib():
         L.mlpg_hip_unit_mse_form.argtypes = [ci, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp]
         L.mlpg_hip_stream_copy.restype = ci
         L.mlpg_hip_stream_copy.argtypes = [ci, vp, vp, vp, ctypes.c_size_t]
+        L.mlpg_hip_gmm_workspace_bytes.restype = ctypes.c_size_t
+        L.mlpg_hip_gmm_workspace_bytes.argtypes = [ctypes.c_int64, ci, ci]
+        L.mlpg_hip_gmm_estep.restype = ci
+        L.mlpg_hip_gmm_estep.argtypes = [ci, vp, vp, vp, vp, vp, vp, ctypes.c_int64, ci, ci, vp, vp, vp, vp, vp, ctypes.c_size_t]
+        L.mlpg_hip_gmm_mstep.restype = ci
+        L.mlpg_hip_gmm_mstep.argtypes = [ci, vp, vp, vp, ctypes.c_int64, ci, ci, cd, vp, vp, vp, vp, ctypes.c_size_t]
+        L.mlpg_hip_gmm_precisions.restype = ci
+        L.mlpg_hip_gmm_precisions.argtypes = [ci, vp, vp, ci, ci, vp, vp, vp]
         if L.mlpg_hip_abi_version() != ABI_VERSION:
             raise HipExtensionError("nnmnkwii_amd: %s has ABI version %d, this binding needs %d -- rebuild it with "
                                     "`python nnmnkwii_amd/csrc/build.py`" % (SO_PATH, L.mlpg_hip_abi_version(), ABI_VERSION))
@@ -1135,6 +1147,78 @@ def gmm_convert(x, posterior, mixture, mu_x, mu_y, A):
                                     _p(mu_y), _p(A), N, D, Dy, M, _p(out))
     _check(rc, "mlpg_hip_gmm_convert")
     return out
+
+
+GMM_MAX_FEATURES, GMM_MAX_COMPONENTS = 128, 64     # the limits of the mlpg_hip_gmm_* entry points
+
+
+def _gmm_x(X):
+    torch = torch_mod()
+    assert X.is_cuda and X.dtype == torch.float64 and X.dim() == 2 and X.is_contiguous()
+    return X.shape
+
+
+def gmm_workspace(device, N, F, K):
+    """A uint8 CUDA tensor of mlpg_hip_gmm_workspace_bytes(N, F, K) bytes (its content is irrelevant)."""
+    torch = torch_mod()
+    need = int(lib().mlpg_hip_gmm_workspace_bytes(int(N), int(F), int(K)))
+    return torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+
+
+def gmm_estep(X, weights, means, prec_chol, log_det, want_resp=True, want_log_prob_norm=False, want_labels=False, want_mean=False,
+              workspace=None):
+    """mlpg_hip_gmm_estep on float64 CUDA tensors: X (N, F), weights (K), means (K, F), prec_chol (K, F, F), log_det (K).
+    Returns (resp (N, K), log_prob_norm (N), labels int32 (N), mean of log_prob_norm as a 0-dim tensor), None where not asked
+    for; enqueued on the current stream."""
+    torch = torch_mod()
+    N, F = _gmm_x(X)
+    K = means.shape[0]
+    dev = X.device
+    for t, shape in ((weights, (K,)), (means, (K, F)), (prec_chol, (K, F, F)), (log_det, (K,))):
+        assert t.shape == shape and t.dtype == torch.float64 and t.is_contiguous() and t.device == dev
+    resp = torch.empty((N, K), dtype=torch.float64, device=dev) if want_resp else None
+    lpn = torch.empty((N,), dtype=torch.float64, device=dev) if want_log_prob_norm else None
+    labels = torch.empty((N,), dtype=torch.int32, device=dev) if want_labels else None
+    mean = torch.empty((), dtype=torch.float64, device=dev) if want_mean else None
+    if want_mean and workspace is None:
+        workspace = gmm_workspace(dev, N, F, K)
+    rc = lib().mlpg_hip_gmm_estep(dev.index, _stream(dev), _p(X), _p(weights), _p(means), _p(prec_chol), _p(log_det), N, F, K,
+                                  _p(resp), _p(lpn), _p(labels), _p(mean), _p(workspace),
+                                  workspace.numel() if workspace is not None else 0)
+    _check(rc, "mlpg_hip_gmm_estep")
+    return resp, lpn, labels, mean
+
+
+def gmm_mstep(X, resp, reg_covar, workspace=None):
+    """mlpg_hip_gmm_mstep on float64 CUDA tensors: X (N, F), resp (N, K) -> (weights (K), means (K, F), covariances (K, F, F))."""
+    torch = torch_mod()
+    N, F = _gmm_x(X)
+    K = resp.shape[1]
+    dev = X.device
+    assert resp.shape == (N, K) and resp.dtype == torch.float64 and resp.is_contiguous() and resp.device == dev
+    weights = torch.empty((K,), dtype=torch.float64, device=dev)
+    means = torch.empty((K, F), dtype=torch.float64, device=dev)
+    cov = torch.empty((K, F, F), dtype=torch.float64, device=dev)
+    if workspace is None:
+        workspace = gmm_workspace(dev, N, F, K)
+    rc = lib().mlpg_hip_gmm_mstep(dev.index, _stream(dev), _p(X), _p(resp), N, F, K, float(reg_covar), _p(weights), _p(means),
+                                  _p(cov), _p(workspace), workspace.numel())
+    _check(rc, "mlpg_hip_gmm_mstep")
+    return weights, means, cov
+
+
+def gmm_precisions(cov):
+    """mlpg_hip_gmm_precisions: covariances (K, F, F) float64 CUDA -> (prec_chol (K, F, F), log_det (K), status int32 (K))."""
+    torch = torch_mod()
+    assert cov.is_cuda and cov.dtype == torch.float64 and cov.dim() == 3 and cov.is_contiguous() and cov.shape[1] == cov.shape[2]
+    K, F, _ = cov.shape
+    dev = cov.device
+    U = torch.zeros((K, F, F), dtype=torch.float64, device=dev)
+    log_det = torch.zeros((K,), dtype=torch.float64, device=dev)
+    status = torch.empty((K,), dtype=torch.int32, device=dev)
+    rc = lib().mlpg_hip_gmm_precisions(dev.index, _stream(dev), _p(cov), F, K, _p(U), _p(log_det), _p(status))
+    _check(rc, "mlpg_hip_gmm_precisions")
+    return U, log_det, status
 
 
 def raise_on_status(status, sd):

@@ -1,7 +1,8 @@
 """GMM-based feature conversion with MLPG on MI355X.
 
 Host-side mirror of /root/reference/nnmnkwii/baseline/gmm.py:46-247 (``MLPGBase``,
-``MLPG``).  The mixture model itself stays with scikit-learn, as in the reference; what
+``MLPG``).  By default the mixture posteriors come from scikit-learn, as in the reference (``posterior="device"`` takes them
+from the E-step kernel of :mod:`nnmnkwii_amd.mixture` instead and keeps them on the GPU); what
 the reference does frame by frame in Python (one ``np.linalg.solve`` per frame and
 mixture, gmm.py:111-113,225-229) is ONE launch of ``mlpg_hip_gmm_convert`` over all frames
 (the M regression matrices ``S_yx S_xx^-1`` are formed once per model on the host), and the
@@ -40,10 +41,17 @@ class MLPGBase(object):
 
     Attributes (same names as the reference): ``num_mixtures, weights, src_means, tgt_means,
     covarXX, covarXY, covarYX, covarYY, px``.
+
+    ``posterior``: "sklearn" (the default: ``px.predict_proba`` / ``px.predict`` on the host, as the reference) or "device" (the
+    float64 E-step kernel, ``mlpg_hip_gmm_estep``; the posteriors, or the arg-max mixtures, stay on the GPU between it and
+    ``mlpg_hip_gmm_convert``).
     """
 
-    def __init__(self, gmm, swap=False, diff=False):
+    def __init__(self, gmm, swap=False, diff=False, *, posterior="sklearn"):
         assert gmm.covariance_type == "full"
+        if posterior not in ("sklearn", "device"):
+            raise ValueError("posterior must be 'sklearn' or 'device', got %r" % (posterior,))
+        self.posterior = posterior
         half = gmm.means_.shape[1] // 2
         self.num_mixtures = gmm.means_.shape[0]
         self.weights = gmm.weights_
@@ -89,17 +97,35 @@ class MLPGBase(object):
         out = _hip.gmm_convert(x, post, mx, f64(self.src_means), f64(self.tgt_means), f64(self._regression()))
         return out.cpu().numpy()
 
+    def _convert_device(self, src, hard=False):
+        """``_convert`` with the posteriors (``hard``: the most likely mixture of each row) taken from the device E-step under
+        p(x) and handed to the conversion kernel without leaving the GPU.  Returns (float64 ndarray, int mixtures or None)."""
+        from .. import mixture as _mix
+        torch = _hip.torch_mod()
+        dev = _hip.require_gpu()
+        f64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)  # noqa: E731
+        x = f64(src)
+        w, mu, U, log_det = _mix._model(self.px, dev)
+        resp, _, labels, _ = _hip.gmm_estep(x, w, mu, U, log_det, want_resp=not hard, want_labels=hard)
+        out = _hip.gmm_convert(x, resp, labels, mu, f64(self.tgt_means), f64(self._regression()))
+        return out.cpu().numpy(), (labels.cpu().numpy() if hard else None)
+
     def _transform_frame(self, src):
         """One frame (D,) -> E[p(y|x)] (gmm.py:97-120)."""
         src = np.asarray(src)
+        if self.posterior == "device":
+            return self._convert_device(np.atleast_2d(src))[0][0]
         posterior = self.px.predict_proba(np.atleast_2d(src))             # (1, M)
         return self._convert(np.atleast_2d(src), posterior)[0]
 
     def transform(self, src):
         if src.ndim != 2:
             return self._transform_frame(src)
-        posterior = self.px.predict_proba(src)                            # (T, M): scikit-learn, as the reference
         tgt = np.zeros_like(src)                                          # dtype of src (gmm.py:89)
+        if self.posterior == "device":
+            tgt[...] = self._convert_device(src)[0]
+            return tgt
+        posterior = self.px.predict_proba(src)                            # (T, M): scikit-learn, as the reference
         tgt[...] = self._convert(src, posterior)
         return tgt
 
@@ -109,7 +135,7 @@ class MLPGBase(object):
         if not utterances:
             return []
         allx = np.concatenate(utterances, axis=0)
-        y = self._convert(allx, self.px.predict_proba(allx))
+        y = self._convert_device(allx)[0] if self.posterior == "device" else self._convert(allx, self.px.predict_proba(allx))
         out, o = [], 0
         for u in utterances:
             t = np.zeros_like(u)
@@ -127,8 +153,8 @@ class MLPG(MLPGBase):
     GPU.  Static-only inputs (feature dim == static dim) take the frame-wise path of ``MLPGBase``.
     """
 
-    def __init__(self, gmm, windows=None, swap=False, diff=False):
-        super(MLPG, self).__init__(gmm, swap, diff)
+    def __init__(self, gmm, windows=None, swap=False, diff=False, *, posterior="sklearn"):
+        super(MLPG, self).__init__(gmm, swap, diff, posterior=posterior)
         if windows is None:
             windows = [(0, 0, np.array([1.0])), (1, 1, np.array([-0.5, 0.0, 0.5]))]
         self.windows = windows
@@ -137,8 +163,11 @@ class MLPG(MLPGBase):
     def transform(self, src):
         if src.shape[1] == self.static_dim:
             return super(MLPG, self).transform(src)
-        mix = self.px.predict(src)                                        # sub-optimum mixture sequence, eq. 37
-        E = self._convert(src, mix=mix)                                   # eq. 22 / 40
+        if self.posterior == "device":
+            E, mix = self._convert_device(src, hard=True)
+        else:
+            mix = self.px.predict(src)                                    # sub-optimum mixture sequence, eq. 37
+            E = self._convert(src, mix=mix)                               # eq. 22 / 40
         dg = lambda a: np.diagonal(a, axis1=1, axis2=2)                   # noqa: E731
         Dm = dg(self.covarYY) - dg(self.covarYX) / dg(self.covarXX) * dg(self.covarXY)   # eq. 23, diagonal approx.
         return _mlpg(E, np.ascontiguousarray(Dm[mix]), self.windows)

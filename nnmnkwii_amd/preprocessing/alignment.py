@@ -229,8 +229,10 @@ class IterativeDTWAligner(object):
     convert X frame-wise with that GMM -> repeat; finally gather the ORIGINAL X along the
     last warping paths.
 
-    The DTW of every iteration is one batched GPU pass over all pairs; the GMM fit stays with
-    scikit-learn (as in the reference) and the frame-wise conversion is
+    The DTW of every iteration is one batched GPU pass over all pairs; the GMM fit is scikit-learn's
+    (as in the reference) unless ``gmm="device"`` asks for the float64 EM kernels of
+    :func:`nnmnkwii_amd.mixture.fit_gaussian_mixture` (started from scikit-learn's own initialisation; the
+    posteriors of the conversion then come from the device E-step too), and the frame-wise conversion is
     :class:`nnmnkwii_amd.baseline.gmm.MLPG` with a static-only window.  Reference behaviours
     kept on purpose: the aligned buffers persist across iterations and only their prefixes are
     rewritten (alignment.py:163-164), the GMM is fitted on the zero padding as well (:175-178), and
@@ -238,10 +240,14 @@ class IterativeDTWAligner(object):
 
     Attributes:
         n_iter, dist, radius, verbose, max_iter_gmm, n_components_gmm: as in the reference.
+        gmm: "sklearn" (the default) or "device".
     """
 
     def __init__(self, n_iter=3, dist=_default_dist, radius=1, max_iter_gmm=100, n_components_gmm=16, verbose=0, *,
-                 tie_rule="first"):
+                 tie_rule="first", gmm="sklearn"):
+        if gmm not in ("sklearn", "device"):
+            raise ValueError("gmm must be 'sklearn' or 'device', got %r" % (gmm,))
+        self.gmm = gmm
         self.tie_rule = tie_rule
         self.n_iter = n_iter
         self.dist = dist
@@ -254,7 +260,9 @@ class IterativeDTWAligner(object):
         from sklearn.mixture import GaussianMixture
 
         from ..baseline.gmm import MLPG
+        from ..mixture import fit_gaussian_mixture
 
+        device_gmm = getattr(self, "gmm", "sklearn") == "device"
         X, Y = XY
         assert X.ndim == 3 and Y.ndim == 3                    # alignment.py:125
         longer = X if X.shape[1] > Y.shape[1] else Y          # :127
@@ -286,10 +294,14 @@ class IterativeDTWAligner(object):
                 for idx in range(N):
                     print("{}, distance: {}".format(idx, dd[idx]))
 
-            gmm = GaussianMixture(n_components=self.n_components_gmm, covariance_type="full", max_iter=self.max_iter_gmm)
             joint = np.concatenate((X_aligned, Y_aligned), axis=-1).reshape(-1, X.shape[-1] * 2)
-            gmm.fit(joint)                                     # :170-178
-            conv = MLPG(gmm, windows=[(0, 0, np.array([1.0]))])   # no delta: frame-wise conversion (:179-180)
+            if device_gmm:                                     # the same fit (zero padding rows included) by the EM kernels
+                gmm = fit_gaussian_mixture(joint, self.n_components_gmm, max_iter=self.max_iter_gmm)
+            else:
+                gmm = GaussianMixture(n_components=self.n_components_gmm, covariance_type="full", max_iter=self.max_iter_gmm)
+                gmm.fit(joint)                                 # :170-178
+            # no delta: frame-wise conversion (:179-180)
+            conv = MLPG(gmm, windows=[(0, 0, np.array([1.0]))], posterior="device" if device_gmm else "sklearn")
             nx = lenx                                          # trim_zeros_frames(Xc[idx]) of this iteration
             converted = conv.transform_batch([Xc[idx][: int(nx[idx])] for idx in range(N)])   # one launch (:181-183)
             for idx in range(N):

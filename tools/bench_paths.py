@@ -19,6 +19,10 @@
         autograd.modspec_batch + torch ops, (c) the fused autograd.modspec_mse_loss
   c5b : (only with --only c5b) forward + backward of the same (512, 2000, 198) batch with gradients for means and variances:
         autograd.multi_stream_mlpg in place against three mlpg_batch on .contiguous() slices plus cat; the epilogue kernel's share
+  gmm : (only with --only gmm) one aligner iteration's joint-GMM fit at config 4 (128 pairs, T in [700, 900], 25 dims: F = 50,
+        K = 16, max_iter = 100) by scikit-learn on the host and by mixture.fit_gaussian_mixture from the same start: wall time,
+        iterations run, milliseconds per EM iteration of each of the three kernels; also written to profiles/gmm_em.json
+        (NNMNKWII_GMM_PROFILE names another file)
 
 Each line carries the GPU time (HIP events on the launch stream), the algorithmic bytes, GB/s, and a
 bounded CPU baseline from the oracle on the same host (the checker, timed like bench.py's cpu_baseline).
@@ -643,6 +647,62 @@ def _run(only, quick, device_index):
                 assert e_m <= tol and e_v <= tol, ("c5b spot check", tag, e_m, e_v)
                 del mq, vq, md, vd, y
             del m, vf, go
+
+    # ---- gmm: the joint-GMM fit of one IterativeDTWAligner iteration at config 4, host and device; only with --only gmm ----
+    if args.only and "gmm" in args.only.split(","):
+        import warnings
+        from sklearn.mixture import GaussianMixture
+        from nnmnkwii_amd.mixture import fit_gaussian_mixture
+        N, D, K = (16 if args.quick else 128), 25, 16
+        rng = np.random.RandomState(1234)
+        X = np.zeros((N, 900, D))
+        Y = np.zeros((N, 900, D))
+        for n in range(N):
+            a, b = rng.randint(700, 901, size=2)
+            X[n, :a] = np.cumsum(rng.randn(a, D), 0) * 0.1
+            Y[n, :b] = np.cumsum(rng.randn(b, D), 0) * 0.1
+        Xa, Ya = DTWAligner().transform((X, Y))
+        joint = np.concatenate((Xa, Ya), axis=-1).reshape(-1, 2 * D)        # zero padding rows included, as the aligner fits it
+        rows, F = joint.shape
+        t0 = time.perf_counter()
+        g0 = GaussianMixture(n_components=K, covariance_type="full", max_iter=0, random_state=0).fit(joint)
+        init_s = time.perf_counter() - t0
+        init = (g0.weights_, g0.means_, g0.covariances_)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            fit_gaussian_mixture(joint, K, max_iter=2, init=init)            # warm-up: code objects, allocator
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            gd = fit_gaussian_mixture(joint, K, max_iter=100, init=init)
+            dev_s = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            gs = GaussianMixture(n_components=K, covariance_type="full", max_iter=100, weights_init=init[0], means_init=init[1],
+                                 precisions_init=g0.precisions_).fit(joint)
+            host_s = time.perf_counter() - t0
+        f64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)  # noqa: E731
+        xd, w, mu, cov = f64(joint), f64(gd.weights_), f64(gd.means_), f64(gd.covariances_)
+        ws = _hip.gmm_workspace(dev, rows, F, K)
+        U, log_det, _ = _hip.gmm_precisions(cov)
+        resp = _hip.gmm_estep(xd, w, mu, U, log_det, want_mean=True, workspace=ws)[0]
+        ms_e = gpu_time(lambda: _hip.gmm_estep(xd, w, mu, U, log_det, want_mean=True, workspace=ws), steps=20)
+        ms_m = gpu_time(lambda: _hip.gmm_mstep(xd, resp, 1e-6, workspace=ws), steps=20)
+        ms_p = gpu_time(lambda: _hip.gmm_precisions(cov), steps=20)
+        rel = lambda a, b: float(np.abs(a - b).max() / np.abs(b).max())  # noqa: E731
+        res = dict(path="gmm-fit-config4", rows=int(rows), F=int(F), K=K, max_iter=100, tol=1e-3, host_threads=os.environ.get("OMP_NUM_THREADS"),
+                   sklearn_init_s=init_s, sklearn_fit_s=host_s, sklearn_iters=int(gs.n_iter_), sklearn_converged=bool(gs.converged_),
+                   sklearn_s_per_iter=host_s / max(int(gs.n_iter_), 1),
+                   device_fit_s=dev_s, device_iters=int(gd.n_iter_), device_converged=bool(gd.converged_),
+                   device_s_per_iter=dev_s / max(int(gd.n_iter_), 1), estep_ms=ms_e, mstep_ms=ms_m, precisions_ms=ms_p,
+                   fit_speedup=host_s / dev_s, means_rel_diff=rel(gd.means_, gs.means_),
+                   lower_bound_device=float(gd.lower_bound_), lower_bound_sklearn=float(gs.lower_bound_),
+                   flops_per_iter=float(rows) * K * F * F * 2 * 2,
+                   note="one aligner iteration's fit, both from the same max_iter=0 start; device_fit_s includes the host-to-device copy "
+                        "of the joint matrix and the per-iteration read-back; kernel times are HIP-event medians on settled clocks")
+        emit(**res)
+        out = os.environ.get("NNMNKWII_GMM_PROFILE") or os.path.join(ROOT, "profiles", "gmm_em.json")
+        with open(out, "w") as fh:
+            json.dump(res, fh, indent=1, sort_keys=True)
+            fh.write("\n")
 
     # ---- c3: unit-variance autograd fwd+bwd ----
     if want("c3"):
