@@ -640,6 +640,48 @@ int mlpg_hip_gmm_precisions(int device, void *stream,
                             int32_t *status);
 
 /*
+ * Float64 k-means for the start of that EM on the device (K7, csrc/kmeans.hip): the two steps scikit-learn's KMeans spends its
+ * time in (sklearn/cluster/_kmeans.py: _kmeans_plusplus, _kmeans_single_lloyd), restated; the draws, the choice among the
+ * candidates and the convergence test stay with the caller (nnmnkwii_amd.mixture.kmeans).  Limits: 1 <= F <= 128 features,
+ * 1 <= K <= 64 clusters, 1 <= C <= 8 candidates, N >= 0 rows; all arrays row-major on the device, float64 unless said otherwise.
+ * Every argument is checked before a device is selected; N == 0 returns 0 and touches nothing.  Both steps read X once, as
+ * x - shift when shift (F doubles, the column means) is not NULL: X itself is never written.  No floating-point atomics: every
+ * sum over rows is kept per slice of rows in row order and added over the slices in index order; two calls on the same inputs
+ * give the same bits.
+ *
+ * mlpg_hip_kmeans_workspace_bytes: the workspace a fit of this shape needs, a function of the shape alone; 0 for sizes outside
+ * the limits.  With S = min(max(ceil(N / 64), 1), 1024) slices (each ceil(ceil(N / 64) / S) tiles of 64 rows) and r(b) = b
+ * rounded up to 256:  r(8 * 8 S) [the seed step's partial pots] + r(8 S K (F + 1)) [partial sums and counts] + r(8 S) [partial
+ * inertia] + r(8 S) [partial changed-label counts] + r(8 K) [squared shift per cluster].
+ *
+ * mlpg_hip_kmeans_seed_step: candidates int32 (C) row indices on the device (an index outside [0, N) is clamped into it),
+ * closest_in (N) or NULL.  d (C, N): d[j][n] = min(closest_in[n], sum_f (x_n - x_candidates[j])_f^2), without the minimum when
+ * closest_in is NULL; pots (C): pots[j] = sum_n d[j][n].  Needs the first region of the workspace only (r(64 S) bytes).
+ *
+ * mlpg_hip_kmeans_lloyd_step: centers (K, F) (in the shifted frame), labels_prev int32 (N).  labels int32 (N): the arg-min over
+ * k of |c_k|^2 - 2 (x_n - shift).c_k, the first of equals (labels may be labels_prev itself); min_dist (N) or NULL:
+ * |x_n - shift - c_label|^2 as the direct sum over the features; sums (K, F) and counts (K): the rows of every cluster added up
+ * and counted, not averaged; centers_out (K, F), written when update_centers != 0: sums / counts where the count is positive,
+ * the old centre elsewhere (relocating an empty cluster is the caller's).  stats, 32 bytes, 8-byte aligned: double shift (sum_k
+ * |centers_out_k - centers_k|^2 added in k order; 0 with update_centers == 0), double inertia (sum_n min_dist_n, computed
+ * whether or not min_dist is stored), int64 changed (rows with labels != labels_prev), int64 empty (clusters with count 0).
+ */
+size_t mlpg_hip_kmeans_workspace_bytes(int64_t N, int F, int K);
+int mlpg_hip_kmeans_seed_step(int device, void *stream, const double *X,
+                              const double *shift, int64_t N, int F,
+                              const int32_t *candidates, int C,
+                              const double *closest_in, double *d,
+                              double *pots, void *workspace,
+                              size_t workspace_bytes);
+int mlpg_hip_kmeans_lloyd_step(int device, void *stream, const double *X,
+                               const double *shift, const double *centers,
+                               const int32_t *labels_prev, int64_t N, int F,
+                               int K, int update_centers, int32_t *labels,
+                               double *min_dist, double *sums, double *counts,
+                               double *centers_out, void *stats,
+                               void *workspace, size_t workspace_bytes);
+
+/*
  * Gather rows along the warping path into zero-padded outputs.  Replaces
  * alignment.py:52-54,72-73:  out[n, k, :] = src[n, path[n, k], :] for
  * k < path_len[n], zeros after.  src (N, Tsrc, D), out (N, Tout, D), same dtype.

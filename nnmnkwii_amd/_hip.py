@@ -69,6 +69,9 @@ EXPORTS = (
     "mlpg_hip_gmm_estep",
     "mlpg_hip_gmm_mstep",
     "mlpg_hip_gmm_precisions",
+    "mlpg_hip_kmeans_workspace_bytes",
+    "mlpg_hip_kmeans_seed_step",
+    "mlpg_hip_kmeans_lloyd_step",
 )
 
 
@@ -221,6 +224,12 @@ def lib():
         L.mlpg_hip_gmm_mstep.argtypes = [ci, vp, vp, vp, ctypes.c_int64, ci, ci, cd, vp, vp, vp, vp, ctypes.c_size_t]
         L.mlpg_hip_gmm_precisions.restype = ci
         L.mlpg_hip_gmm_precisions.argtypes = [ci, vp, vp, ci, ci, vp, vp, vp]
+        L.mlpg_hip_kmeans_workspace_bytes.restype = ctypes.c_size_t
+        L.mlpg_hip_kmeans_workspace_bytes.argtypes = [ctypes.c_int64, ci, ci]
+        L.mlpg_hip_kmeans_seed_step.restype = ci
+        L.mlpg_hip_kmeans_seed_step.argtypes = [ci, vp, vp, vp, ctypes.c_int64, ci, vp, ci, vp, vp, vp, vp, ctypes.c_size_t]
+        L.mlpg_hip_kmeans_lloyd_step.restype = ci
+        L.mlpg_hip_kmeans_lloyd_step.argtypes = [ci, vp, vp, vp, vp, vp, ctypes.c_int64, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t]
         if L.mlpg_hip_abi_version() != ABI_VERSION:
             raise HipExtensionError("nnmnkwii_amd: %s has ABI version %d, this binding needs %d -- rebuild it with "
                                     "`python nnmnkwii_amd/csrc/build.py`" % (SO_PATH, L.mlpg_hip_abi_version(), ABI_VERSION))
@@ -1219,6 +1228,69 @@ def gmm_precisions(cov):
     rc = lib().mlpg_hip_gmm_precisions(dev.index, _stream(dev), _p(cov), F, K, _p(U), _p(log_det), _p(status))
     _check(rc, "mlpg_hip_gmm_precisions")
     return U, log_det, status
+
+
+KMEANS_MAX_CANDIDATES = 8     # candidates of one mlpg_hip_kmeans_seed_step
+
+
+def kmeans_workspace(device, N, F, K):
+    """A uint8 CUDA tensor of mlpg_hip_kmeans_workspace_bytes(N, F, K) bytes (its content is irrelevant)."""
+    torch = torch_mod()
+    need = int(lib().mlpg_hip_kmeans_workspace_bytes(int(N), int(F), int(K)))
+    return torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+
+
+def kmeans_seed_step(X, shift, candidates, closest=None, workspace=None):
+    """mlpg_hip_kmeans_seed_step on CUDA tensors: X (N, F) float64, shift (F) float64 or None, candidates int32 (C), closest (N)
+    float64 or None -> (d (C, N), pots (C)); enqueued on the current stream."""
+    torch = torch_mod()
+    N, F = _gmm_x(X)
+    dev = X.device
+    C = candidates.shape[0]
+    assert candidates.shape == (C,) and candidates.dtype == torch.int32 and candidates.is_contiguous() and candidates.device == dev
+    for t, shape in ((shift, (F,)), (closest, (N,))):
+        assert t is None or (t.shape == shape and t.dtype == torch.float64 and t.is_contiguous() and t.device == dev)
+    d = torch.empty((C, N), dtype=torch.float64, device=dev)
+    pots = torch.empty((C,), dtype=torch.float64, device=dev)
+    if workspace is None:
+        workspace = kmeans_workspace(dev, N, F, 1)
+    rc = lib().mlpg_hip_kmeans_seed_step(dev.index, _stream(dev), _p(X), _p(shift), N, F, _p(candidates), C, _p(closest), _p(d),
+                                         _p(pots), _p(workspace), workspace.numel())
+    _check(rc, "mlpg_hip_kmeans_seed_step")
+    return d, pots
+
+
+def kmeans_lloyd_step(X, shift, centers, labels_prev, update_centers=True, want_min_dist=False, workspace=None):
+    """mlpg_hip_kmeans_lloyd_step on CUDA tensors: X (N, F) float64, shift (F) float64 or None, centers (K, F) float64,
+    labels_prev int32 (N) -> (labels int32 (N), min_dist (N) or None, sums (K, F), counts (K), centers_out (K, F) or None, stats).
+    stats: int64 (4) holding the bits of (double shift, double inertia, int64 changed, int64 empty) -- kmeans_stats reads it."""
+    torch = torch_mod()
+    N, F = _gmm_x(X)
+    dev = X.device
+    K = centers.shape[0]
+    assert labels_prev.shape == (N,) and labels_prev.dtype == torch.int32 and labels_prev.is_contiguous() and labels_prev.device == dev
+    for t, shape in ((shift, (F,)), (centers, (K, F))):
+        assert t is None or (t.shape == shape and t.dtype == torch.float64 and t.is_contiguous() and t.device == dev)
+    labels = torch.empty((N,), dtype=torch.int32, device=dev)
+    min_dist = torch.empty((N,), dtype=torch.float64, device=dev) if want_min_dist else None
+    sums = torch.empty((K, F), dtype=torch.float64, device=dev)
+    counts = torch.empty((K,), dtype=torch.float64, device=dev)
+    centers_out = torch.empty((K, F), dtype=torch.float64, device=dev) if update_centers else None
+    stats = torch.empty((4,), dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = kmeans_workspace(dev, N, F, K)
+    rc = lib().mlpg_hip_kmeans_lloyd_step(dev.index, _stream(dev), _p(X), _p(shift), _p(centers), _p(labels_prev), N, F, K,
+                                          1 if update_centers else 0, _p(labels), _p(min_dist), _p(sums), _p(counts),
+                                          _p(centers_out), _p(stats), _p(workspace), workspace.numel())
+    _check(rc, "mlpg_hip_kmeans_lloyd_step")
+    return labels, min_dist, sums, counts, centers_out, stats
+
+
+def kmeans_stats(stats):
+    """(shift, inertia, changed, empty) of a Lloyd step's statistics record: the step's one read-back."""
+    raw = stats.cpu().numpy()
+    fl = raw.view(np.float64)
+    return float(fl[0]), float(fl[1]), int(raw[2]), int(raw[3])
 
 
 def raise_on_status(status, sd):

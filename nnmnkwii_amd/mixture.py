@@ -4,6 +4,9 @@ scikit-learn's float64 EM -- ``_e_step`` / ``_m_step`` of ``sklearn.mixture.Gaus
 ``csrc/gmm_em.hip`` (``mlpg_hip_gmm_estep`` / ``_mstep`` / ``_precisions``).  The result of :func:`fit_gaussian_mixture` is an
 ordinary fitted ``GaussianMixture``: ``baseline.gmm.MLPG(gmm)`` takes it unchanged.  Only ``covariance_type="full"`` and one
 initialisation (``n_init=1``); at most 128 features and 64 components.  There is no CPU fallback.
+
+:func:`kmeans` is scikit-learn's ``KMeans(n_init=1)`` -- k-means++ seeding and Lloyd iterations -- on the kernels of
+``csrc/kmeans.hip``; ``fit_gaussian_mixture(..., init="kmeans")`` starts the EM from it without X leaving the device.
 """
 import warnings
 
@@ -111,6 +114,130 @@ def _start(X_host, n_components, reg_covar, init, random_state):
     return w, mu, cov
 
 
+def _relocate(xc, centers, labels, min_dist, sums, counts):
+    """scikit-learn's _relocate_empty_clusters_dense by torch operations (the rare path): the rows farthest from their centre, one
+    per empty cluster in descending order, become the empty clusters' sums with count 1 and leave their old clusters.  Returns
+    (new centres, their shift as a 0-dim tensor); the labels stay."""
+    torch = _hip.torch_mod()
+    sums, counts = sums.clone(), counts.clone()
+    empty = torch.nonzero(counts == 0).flatten()
+    far = torch.topk(min_dist, int(empty.numel())).indices
+    for new, n in zip(empty.tolist(), far.tolist()):
+        old = int(labels[n])
+        row = xc(n)
+        sums[old] -= row
+        sums[new] = row
+        counts[new] = 1.0
+        counts[old] -= 1.0
+    pos = counts > 0
+    new_centers = torch.where(pos[:, None], sums / torch.where(pos, counts, torch.ones_like(counts))[:, None], sums)
+    return new_centers, torch.sum(torch.square(new_centers - centers))
+
+
+def _kmeans_device(x, K, max_iter, tol, random_state, init):
+    """k-means on float64 CUDA rows: (labels int32 (N), centres (K, F), inertia, n_iter), the tensors on x's device."""
+    from sklearn.utils import check_random_state
+    torch = _hip.torch_mod()
+    N, F = x.shape
+    dev = x.device
+    rs = check_random_state(random_state)
+    tol_abs = float(torch.var(x, dim=0, unbiased=False).mean()) * tol if tol != 0 else 0.0
+    shift = x.mean(dim=0).contiguous()
+    ws = _hip.kmeans_workspace(dev, N, F, K)
+
+    if init is None:
+        # k-means++: the draws on the host in scikit-learn's order, everything over the rows on the device
+        trials = 2 + int(np.log(K))
+        first = rs.choice(N, p=np.ones(N) / N)
+        idx = torch.empty((K,), dtype=torch.int64, device=dev)
+        idx[0] = int(first)
+        d, pots = _hip.kmeans_seed_step(x, shift, idx[:1].to(torch.int32), None, workspace=ws)
+        closest, pot = d[0], float(pots.cpu()[0])
+        for c in range(1, K):
+            rand = torch.from_numpy(rs.uniform(size=trials) * pot).to(dev)
+            cand = torch.searchsorted(torch.cumsum(closest, dim=0), rand).clamp_(max=N - 1)
+            d, pots = _hip.kmeans_seed_step(x, shift, cand.to(torch.int32), closest, workspace=ws)
+            back = pots.cpu().numpy()                       # the centre's one read-back: the pots of its candidates
+            best = int(np.argmin(back))
+            closest, pot = d[best], float(back[best])
+            idx[c] = cand[best]
+        centers = (x[idx] - shift).contiguous()
+    else:
+        centers = (_to_dev(init, dev) - shift).contiguous()
+
+    labels_prev = torch.full((N,), -1, dtype=torch.int32, device=dev)
+    labels, strict, relocated, n_iter = labels_prev, False, False, 0
+    for n_iter in range(1, int(max_iter) + 1):
+        labels, _, sums, counts, new_centers, stats = _hip.kmeans_lloyd_step(x, shift, centers, labels_prev, workspace=ws)
+        move, _, changed, empty = _hip.kmeans_stats(stats)             # the iteration's one read-back
+        relocated = empty > 0
+        if relocated:
+            # the same step again for the distances to the old centres (the same bits), then scikit-learn's relocation
+            labels, min_dist, sums, counts, _, _ = _hip.kmeans_lloyd_step(x, shift, centers, labels_prev, want_min_dist=True,
+                                                                          workspace=ws)
+            new_centers, move_t = _relocate(lambda n: x[n] - shift, centers, labels, min_dist, sums, counts)
+            new_centers, move = new_centers.contiguous(), float(move_t)
+        centers = new_centers
+        if changed == 0:
+            strict = True
+            break
+        if move <= tol_abs:
+            break
+        labels_prev = labels
+    # inertia against the final centres; without strict convergence the labels are assigned once more
+    last, min_dist, _, _, _, stats = _hip.kmeans_lloyd_step(x, shift, centers, labels, update_centers=False,
+                                                            want_min_dist=strict and relocated, workspace=ws)
+    if not strict:
+        labels = last
+        inertia = _hip.kmeans_stats(stats)[1]
+    elif relocated:
+        inertia = float(torch.sum(torch.square(x - shift - centers[labels.long()])))
+    else:
+        inertia = _hip.kmeans_stats(stats)[1]        # unchanged labels gave unchanged centres: `last` is `labels`
+    return labels, centers + shift, inertia, n_iter
+
+
+def kmeans(X, n_clusters, *, max_iter=300, tol=1e-4, random_state=None, init=None):
+    """scikit-learn's ``KMeans(n_clusters, n_init=1, max_iter=max_iter, tol=tol, random_state=random_state).fit(X)`` on the GPU:
+    returns ``(labels, centers, inertia, n_iter)``.
+
+    X: (N, F) ndarray of any float dtype -- computed in float64 (scikit-learn would stay in float32 for float32 input); int64
+    labels and float64 centres come back as ndarrays -- or a float64 CUDA tensor, used in place (never modified: the column means
+    are subtracted as the rows are read); int32 labels and the centres come back as CUDA tensors.  ``init``: None for k-means++,
+    or a (K, F) array of centres.  The draws of k-means++ come from ``check_random_state(random_state)`` on the host in
+    scikit-learn's order -- with ``random_state=None`` from numpy's global generator, exactly as a host fit consumes it --; per
+    seeded centre the pots of its candidates are read back, per Lloyd iteration one 32-byte record.  An iteration that leaves a
+    cluster empty relocates it as scikit-learn does.  1 <= F <= 128, 1 <= n_clusters <= 64 and n_clusters <= N.
+    """
+    K = int(n_clusters)
+    x, was_tensor = _device_rows(X)
+    N, F = x.shape
+    _check_limits(F, K)
+    if N < K:
+        raise ValueError("n_samples=%d should be >= n_clusters=%d." % (N, K))
+    if init is not None and tuple(np.shape(init) if not _is_tensor(init) else init.shape) != (K, F):
+        raise ValueError("init must hold %d centres of %d features" % (K, F))
+    if _is_tensor(init):
+        init = init.detach().cpu().numpy()
+    labels, centers, inertia, n_iter = _kmeans_device(x, K, max_iter, tol, random_state, init)
+    if was_tensor:
+        return labels, centers, inertia, n_iter
+    return labels.cpu().numpy().astype(np.int64), centers.cpu().numpy(), inertia, n_iter
+
+
+def _kmeans_start(x, K, reg_covar, random_state, ws):
+    """(weights, means, covariances) on the device as GaussianMixture._initialize_parameters(init_params="kmeans") gives them:
+    the one-hot responsibilities of the device k-means through the M-step, weights nk / N (not renormalised)."""
+    torch = _hip.torch_mod()
+    N = x.shape[0]
+    labels = _kmeans_device(x, K, 300, 1e-4, random_state, None)[0].long()
+    resp = torch.zeros((N, K), dtype=torch.float64, device=x.device)
+    resp.scatter_(1, labels[:, None], 1.0)
+    _, mu, cov = _hip.gmm_mstep(x, resp, reg_covar, workspace=ws)
+    nk = torch.bincount(labels, minlength=K).to(torch.float64) + 10.0 * np.finfo(np.float64).eps
+    return (nk / N).contiguous(), mu, cov
+
+
 def fit_gaussian_mixture(X, n_components, *, max_iter=100, tol=1e-3, reg_covar=1e-6, init=None, random_state=None):
     """Fit a full-covariance Gaussian mixture by EM on the GPU; returns a fitted ``sklearn.mixture.GaussianMixture``.
 
@@ -121,8 +248,9 @@ def fit_gaussian_mixture(X, n_components, *, max_iter=100, tol=1e-3, reg_covar=1
 
     X: (N, F) ndarray of any float dtype -- computed and returned in float64 (scikit-learn would stay in float32 for float32
     input) -- or a float64 CUDA tensor, used in place.  ``init``: None (scikit-learn's own initialisation on the host:
-    ``GaussianMixture(..., max_iter=0, random_state=random_state).fit(X)``, the same k-means draw a host fit would start from), a
-    fitted ``GaussianMixture``, or a ``(weights, means, covariances)`` triple.  1 <= F <= 128, 1 <= n_components <= 64; a
+    ``GaussianMixture(..., max_iter=0, random_state=random_state).fit(X)``, the same k-means draw a host fit would start from),
+    ``"kmeans"`` (the same initialisation by :func:`kmeans` and the M-step on the device, from the same draws: X never leaves the
+    device), a fitted ``GaussianMixture``, or a ``(weights, means, covariances)`` triple.  1 <= F <= 128, 1 <= n_components <= 64; a
     covariance that is not positive definite raises scikit-learn's ``ValueError``.
     """
     from sklearn.exceptions import ConvergenceWarning
@@ -135,12 +263,20 @@ def fit_gaussian_mixture(X, n_components, *, max_iter=100, tol=1e-3, reg_covar=1
     if N < 1:
         raise ValueError("fit_gaussian_mixture needs at least one row")
     dev = x.device
-    w0, mu0, cov0 = _start(lambda: x.cpu().numpy() if was_tensor else np.ascontiguousarray(X, dtype=np.float64), K, reg_covar, init,
-                           random_state)
-    if mu0.shape[1] != F:
-        raise ValueError("X has %d features, init has %d" % (F, mu0.shape[1]))
-    w, mu, cov = _to_dev(w0, dev), _to_dev(mu0, dev), _to_dev(cov0, dev)
     ws = _hip.gmm_workspace(dev, N, F, K)
+    if isinstance(init, str):
+        if init != "kmeans":
+            raise ValueError("init must be None, 'kmeans', a fitted GaussianMixture or a (weights, means, covariances) triple; got %r"
+                             % (init,))
+        if N < K:
+            raise ValueError("n_samples=%d should be >= n_components=%d." % (N, K))
+        w, mu, cov = _kmeans_start(x, K, reg_covar, random_state, ws)
+    else:
+        w0, mu0, cov0 = _start(lambda: x.cpu().numpy() if was_tensor else np.ascontiguousarray(X, dtype=np.float64), K, reg_covar,
+                               init, random_state)
+        if mu0.shape[1] != F:
+            raise ValueError("X has %d features, init has %d" % (F, mu0.shape[1]))
+        w, mu, cov = _to_dev(w0, dev), _to_dev(mu0, dev), _to_dev(cov0, dev)
 
     U, log_det, status = _hip.gmm_precisions(cov)
     if bool(status.any().item()):

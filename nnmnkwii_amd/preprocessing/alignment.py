@@ -231,8 +231,10 @@ class IterativeDTWAligner(object):
 
     The DTW of every iteration is one batched GPU pass over all pairs; the GMM fit is scikit-learn's
     (as in the reference) unless ``gmm="device"`` asks for the float64 EM kernels of
-    :func:`nnmnkwii_amd.mixture.fit_gaussian_mixture` (started from scikit-learn's own initialisation; the
-    posteriors of the conversion then come from the device E-step too), and the frame-wise conversion is
+    :func:`nnmnkwii_amd.mixture.fit_gaussian_mixture` (started from scikit-learn's own initialisation on the host, or
+    with ``gmm_init="kmeans-device"`` from the same k-means on the device, :func:`nnmnkwii_amd.mixture.kmeans`: an iteration
+    then calls neither ``KMeans.fit`` nor ``GaussianMixture.fit``; the posteriors of the conversion come from the device
+    E-step too), and the frame-wise conversion is
     :class:`nnmnkwii_amd.baseline.gmm.MLPG` with a static-only window.  Reference behaviours
     kept on purpose: the aligned buffers persist across iterations and only their prefixes are
     rewritten (alignment.py:163-164), the GMM is fitted on the zero padding as well (:175-178), and
@@ -241,13 +243,19 @@ class IterativeDTWAligner(object):
     Attributes:
         n_iter, dist, radius, verbose, max_iter_gmm, n_components_gmm: as in the reference.
         gmm: "sklearn" (the default) or "device".
+        gmm_init: "sklearn" (the default) or "kmeans-device" (with gmm="device" only).
     """
 
     def __init__(self, n_iter=3, dist=_default_dist, radius=1, max_iter_gmm=100, n_components_gmm=16, verbose=0, *,
-                 tie_rule="first", gmm="sklearn"):
+                 tie_rule="first", gmm="sklearn", gmm_init="sklearn"):
         if gmm not in ("sklearn", "device"):
             raise ValueError("gmm must be 'sklearn' or 'device', got %r" % (gmm,))
+        if gmm_init not in ("sklearn", "kmeans-device"):
+            raise ValueError("gmm_init must be 'sklearn' or 'kmeans-device', got %r" % (gmm_init,))
+        if gmm_init == "kmeans-device" and gmm != "device":
+            raise ValueError("gmm_init='kmeans-device' needs gmm='device'")
         self.gmm = gmm
+        self.gmm_init = gmm_init
         self.tie_rule = tie_rule
         self.n_iter = n_iter
         self.dist = dist
@@ -296,7 +304,8 @@ class IterativeDTWAligner(object):
 
             joint = np.concatenate((X_aligned, Y_aligned), axis=-1).reshape(-1, X.shape[-1] * 2)
             if device_gmm:                                     # the same fit (zero padding rows included) by the EM kernels
-                gmm = fit_gaussian_mixture(joint, self.n_components_gmm, max_iter=self.max_iter_gmm)
+                gmm = fit_gaussian_mixture(joint, self.n_components_gmm, max_iter=self.max_iter_gmm,
+                                           init="kmeans" if getattr(self, "gmm_init", "sklearn") == "kmeans-device" else None)
             else:
                 gmm = GaussianMixture(n_components=self.n_components_gmm, covariance_type="full", max_iter=self.max_iter_gmm)
                 gmm.fit(joint)                                 # :170-178

@@ -23,6 +23,10 @@
         K = 16, max_iter = 100) by scikit-learn on the host and by mixture.fit_gaussian_mixture from the same start: wall time,
         iterations run, milliseconds per EM iteration of each of the three kernels; also written to profiles/gmm_em.json
         (NNMNKWII_GMM_PROFILE names another file)
+  kmeans : (only with --only kmeans) the start of that fit on the same joint matrix with one seed: GaussianMixture(max_iter=0).fit
+        on the host against mixture.fit_gaussian_mixture(init="kmeans", max_iter=0): wall time of both, Lloyd iterations of both,
+        milliseconds per seed step and per Lloyd step; also written to profiles/kmeans.json (NNMNKWII_KMEANS_PROFILE names
+        another file)
 
 Each line carries the GPU time (HIP events on the launch stream), the algorithmic bytes, GB/s, and a
 bounded CPU baseline from the oracle on the same host (the checker, timed like bench.py's cpu_baseline).
@@ -648,12 +652,9 @@ def _run(only, quick, device_index):
                 del mq, vq, md, vd, y
             del m, vf, go
 
-    # ---- gmm: the joint-GMM fit of one IterativeDTWAligner iteration at config 4, host and device; only with --only gmm ----
-    if args.only and "gmm" in args.only.split(","):
-        import warnings
-        from sklearn.mixture import GaussianMixture
-        from nnmnkwii_amd.mixture import fit_gaussian_mixture
-        N, D, K = (16 if args.quick else 128), 25, 16
+    def config4_joint():
+        """The joint matrix one IterativeDTWAligner iteration fits at config 4 (zero padding rows included, as the aligner fits it)."""
+        N, D = (16 if args.quick else 128), 25
         rng = np.random.RandomState(1234)
         X = np.zeros((N, 900, D))
         Y = np.zeros((N, 900, D))
@@ -662,7 +663,15 @@ def _run(only, quick, device_index):
             X[n, :a] = np.cumsum(rng.randn(a, D), 0) * 0.1
             Y[n, :b] = np.cumsum(rng.randn(b, D), 0) * 0.1
         Xa, Ya = DTWAligner().transform((X, Y))
-        joint = np.concatenate((Xa, Ya), axis=-1).reshape(-1, 2 * D)        # zero padding rows included, as the aligner fits it
+        return np.concatenate((Xa, Ya), axis=-1).reshape(-1, 2 * D)
+
+    # ---- gmm: the joint-GMM fit of one IterativeDTWAligner iteration at config 4, host and device; only with --only gmm ----
+    if args.only and "gmm" in args.only.split(","):
+        import warnings
+        from sklearn.mixture import GaussianMixture
+        from nnmnkwii_amd.mixture import fit_gaussian_mixture
+        K = 16
+        joint = config4_joint()
         rows, F = joint.shape
         t0 = time.perf_counter()
         g0 = GaussianMixture(n_components=K, covariance_type="full", max_iter=0, random_state=0).fit(joint)
@@ -700,6 +709,56 @@ def _run(only, quick, device_index):
                         "of the joint matrix and the per-iteration read-back; kernel times are HIP-event medians on settled clocks")
         emit(**res)
         out = os.environ.get("NNMNKWII_GMM_PROFILE") or os.path.join(ROOT, "profiles", "gmm_em.json")
+        with open(out, "w") as fh:
+            json.dump(res, fh, indent=1, sort_keys=True)
+            fh.write("\n")
+
+    # ---- kmeans: the start of that fit (k-means, then one M-step), host and device, same data and seed; only with --only kmeans ----
+    if args.only and "kmeans" in args.only.split(","):
+        import warnings
+        from sklearn.cluster import KMeans
+        from sklearn.mixture import GaussianMixture
+        from sklearn.utils import check_random_state
+        from nnmnkwii_amd import mixture
+        K, seed = 16, 0
+        joint = config4_joint()
+        rows, F = joint.shape
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            t0 = time.perf_counter()
+            g0 = GaussianMixture(n_components=K, covariance_type="full", max_iter=0, random_state=seed).fit(joint)
+            host_s = time.perf_counter() - t0
+            km = KMeans(n_clusters=K, n_init=1, random_state=check_random_state(seed)).fit(joint)   # the same draws: its n_iter_
+            mixture.fit_gaussian_mixture(joint, K, init="kmeans", max_iter=0, random_state=seed)   # warm-up: code objects, allocator
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            gd = mixture.fit_gaussian_mixture(joint, K, init="kmeans", max_iter=0, random_state=seed)
+            dev_s = time.perf_counter() - t0
+        xd = torch.from_numpy(joint).to(dev)
+        t0 = time.perf_counter()
+        labels, centers, inertia, n_iter = mixture.kmeans(xd, K, random_state=seed)
+        torch.cuda.synchronize()
+        resident_s = time.perf_counter() - t0
+        shift = xd.mean(dim=0).contiguous()
+        ws = _hip.kmeans_workspace(dev, rows, F, K)
+        cand = torch.arange(0, 5 * 1000, 1000, dtype=torch.int32, device=dev) % rows      # 2 + int(log 16) = 4 trials; 5 is no faster case
+        closest = _hip.kmeans_seed_step(xd, shift, cand[:1], None, workspace=ws)[0][0].contiguous()
+        ms_seed = gpu_time(lambda: _hip.kmeans_seed_step(xd, shift, cand[:4], closest, workspace=ws), steps=20)
+        cen = (centers - shift).contiguous()
+        ms_lloyd = gpu_time(lambda: _hip.kmeans_lloyd_step(xd, shift, cen, labels, workspace=ws), steps=20)
+        rel = lambda a, b: float(np.abs(a - b).max() / np.abs(b).max())  # noqa: E731
+        res = dict(path="kmeans-start-config4", rows=int(rows), F=int(F), K=K, seed=seed, host_threads=os.environ.get("OMP_NUM_THREADS"),
+                   sklearn_start_s=host_s, device_start_s=dev_s, start_speedup=host_s / dev_s, device_kmeans_resident_s=resident_s,
+                   sklearn_lloyd_iters=int(km.n_iter_), device_lloyd_iters=int(n_iter),
+                   labels_equal=bool(np.array_equal(labels.cpu().numpy(), km.labels_)), seed_step_ms=ms_seed, lloyd_step_ms=ms_lloyd,
+                   lloyd_step_gb_s=rows * F * 8 / (ms_lloyd * 1e6), means_rel_diff=rel(gd.means_, g0.means_),
+                   covariances_rel_diff=rel(gd.covariances_, g0.covariances_),
+                   note="GaussianMixture(max_iter=0).fit on the host against fit_gaussian_mixture(init='kmeans', max_iter=0) from numpy "
+                        "input (device_start_s includes the host-to-device copy of the joint matrix and every read-back); "
+                        "device_kmeans_resident_s: mixture.kmeans on the matrix already on the device; kernel times are HIP-event "
+                        "medians on settled clocks, the seed step with 4 candidates")
+        emit(**res)
+        out = os.environ.get("NNMNKWII_KMEANS_PROFILE") or os.path.join(ROOT, "profiles", "kmeans.json")
         with open(out, "w") as fh:
             json.dump(res, fh, indent=1, sort_keys=True)
             fh.write("\n")
