@@ -2,20 +2,9 @@
 // per-system view of the inputs and the on-the-fly assembly of one column of
 // the banded precision matrix (natural order, any window set).
 #pragma once
-#include "common.h"
+#include "device_prims.h"
 
 namespace mlpg {
-
-template <typename T>
-__device__ __forceinline__ double recip_in_dtype(T v);
-template <>
-__device__ __forceinline__ double recip_in_dtype<float>(float v) {
-  return (double)__fdiv_rn(1.0f, v);  // reciprocal evaluated in float32 (_mlpg.py:188)
-}
-template <>
-__device__ __forceinline__ double recip_in_dtype<double>(double v) {
-  return 1.0 / v;
-}
 
 // One (utterance b, static dim d) system as the kernels see it.
 template <typename TIN, bool BWD>

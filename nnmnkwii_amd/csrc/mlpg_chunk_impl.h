@@ -55,48 +55,9 @@ struct Args {
   double cpad[kMaxNw][5];   // coefficients, zero padded to [-EXT, EXT] (index j + EXT)
 };
 
-// ---- buffer loads / stores: wave-uniform descriptor, row offset in an SGPR, this lane's byte offset in one VGPR (a plain
-// pointer per lane costs two address registers and a 64-bit add per access: this kernel has neither to spare) ----
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base) {
-  const unsigned long long u = (unsigned long long)base;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-  return __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0, 0x7fffffff, 0x00020000);
-}
-template <typename T>
-__device__ __forceinline__ T ld_buf(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff);
-template <>
-__device__ __forceinline__ double ld_buf<double>(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff) {
-  const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, loff, soff, 0);
-  return __longlong_as_double((long long)(((unsigned long long)v.y << 32) | v.x));
-}
-template <>
-__device__ __forceinline__ float ld_buf<float>(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff) {
-  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, loff, soff, 0));
-}
-__device__ __forceinline__ void st_buf(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff, double v) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  const u32x2 w = {(unsigned)u, (unsigned)(u >> 32)};
-  __builtin_amdgcn_raw_buffer_store_b64(w, rs, loff, soff, 0);
-}
-__device__ __forceinline__ void st_buf(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, loff, soff, 0);
-}
-
-__device__ __forceinline__ double fast_rcp(double d) {
-  double x = __builtin_amdgcn_rcp(d);
-  x = __builtin_fma(__builtin_fma(-d, x, 1.0), x, x);
-  x = __builtin_fma(__builtin_fma(-d, x, 1.0), x, x);
-  return x;
-}
-// 1 / var: float32 inputs keep the reference's float32 reciprocal exactly (_mlpg.py:188); float64 to ~1 ulp (hardware seed + two
-// Newton steps, as the strip and wave kernels: a correctly rounded division is 25 instructions, three per frame)
-template <typename T>
-__device__ __forceinline__ double tau_of(T v);
-template <>
-__device__ __forceinline__ double tau_of<float>(float v) { return recip_in_dtype<float>(v); }
-template <>
-__device__ __forceinline__ double tau_of<double>(double v) { return fast_rcp(v); }
+// Buffer loads / stores (device_prims.h: make_rsrc, buf_ld, buf_st): wave-uniform descriptor, row offset in an SGPR, this lane's byte
+// offset in one VGPR (a plain pointer per lane costs two address registers and a 64-bit add per access: this kernel has neither to
+// spare).  1 / var is tau_of, as in the strip and wave kernels.
 
 // BWD (paramgen/_mlpg.py:202-281, mlpg_grad): the same matrix, the right-hand side is grad_out, and pass 3 ends with
 // grad[t, w * sd + d] = tau_w[t] * sum_k c_w[l + k] z[t + k].  A row needs z up to EXT frames to its right, so a chunk writes the
@@ -128,7 +89,7 @@ __global__ __launch_bounds__(kW * 64, 2) void chunk_kernel(const Problem p, cons
   if (f0 >= T) {  // nothing of the utterance in this chunk
     if (P3 && lane_ok)
       for (int r = 0; r < C && f0 + r < Tmax; ++r)
-        for (int w = 0; w < (BWD ? a.nw : 1); ++w) st_buf(ors, (unsigned)(f0 + r) * ldo_bytes + (unsigned)w * owin_bytes, ooff, (TOUT)0);
+        for (int w = 0; w < (BWD ? a.nw : 1); ++w) buf_st(ors, (unsigned)(f0 + r) * ldo_bytes + (unsigned)w * owin_bytes, ooff, (TOUT)0);
     return;
   }
   // forward: the means (window-major columns, stride ld_in); backward: grad_out (one column per dim, stride ld_gout)
@@ -145,7 +106,7 @@ __global__ __launch_bounds__(kW * 64, 2) void chunk_kernel(const Problem p, cons
   double tau_g[kMaxNw];
 #pragma unroll
   for (int w = 0; w < kMaxNw; ++w)
-    tau_g[w] = (VM == MLPG_HIP_VAR_GLOBAL && w < nw) ? tau_of<TIN>(ld_buf<TIN>(vrs, (unsigned)w * win_bytes, loff)) : 1.0;
+    tau_g[w] = (VM == MLPG_HIP_VAR_GLOBAL && w < nw) ? tau_of<TIN>(buf_ld<TIN>(vrs, (unsigned)w * win_bytes, loff)) : 1.0;
   const double first = c == 0 ? 0.0 : 1.0;  // chunk 0: columns left of frame 0 do not exist
 
   // pass 3: the neighbouring separators' solutions
@@ -193,9 +154,9 @@ __global__ __launch_bounds__(kW * 64, 2) void chunk_kernel(const Problem p, cons
       rv[s][w] = (TIN)1;
       rm[s][w] = (TIN)0;
       if (fl && (FAST || w < nw)) {
-        if (VM == MLPG_HIP_VAR_FRAME) rv[s][w] = ld_buf<TIN>(vrs, (unsigned)t * ld_bytes + (unsigned)w * win_bytes, loff);
-        if (!BWD) rm[s][w] = ld_buf<TIN>(mrs, (unsigned)t * ld_bytes + (unsigned)w * win_bytes, loff);
-        else if (w == 0) rm[s][0] = ld_buf<TIN>(mrs, (unsigned)t * ldg_bytes, loff);
+        if (VM == MLPG_HIP_VAR_FRAME) rv[s][w] = buf_ld<TIN>(vrs, (unsigned)t * ld_bytes + (unsigned)w * win_bytes, loff);
+        if (!BWD) rm[s][w] = buf_ld<TIN>(mrs, (unsigned)t * ld_bytes + (unsigned)w * win_bytes, loff);
+        else if (w == 0) rm[s][0] = buf_ld<TIN>(mrs, (unsigned)t * ldg_bytes, loff);
       }
     }
   };
@@ -283,7 +244,7 @@ __global__ __launch_bounds__(kW * 64, 2) void chunk_kernel(const Problem p, cons
         row[k] = num * dinv[r - k];
       } else {
         // separator row against an earlier separator row: a Schur entry
-        if (!P3) st_buf(rrs, (unsigned)(G::oSRR + tri(r - I, r - k - I)) * 512u, roff, num);
+        if (!P3) buf_st(rrs, (unsigned)(G::oSRR + tri(r - I, r - k - I)) * 512u, roff, num);
       }
     }
     double diag = A[0];
@@ -328,17 +289,17 @@ __global__ __launch_bounds__(kW * 64, 2) void chunk_kernel(const Problem p, cons
       dinv[r] = 0.0;
       ub[r] = yb;
       if (!P3) {  // a separator row: its part of the record is final (later rows do not pivot on it)
-        st_buf(rrs, (unsigned)(G::oSRR + tri(r - I, r - I)) * 512u, roff, diag);
-        st_buf(rrs, (unsigned)(G::oGR + r - I) * 512u, roff, yb);
+        buf_st(rrs, (unsigned)(G::oSRR + tri(r - I, r - I)) * 512u, roff, diag);
+        buf_st(rrs, (unsigned)(G::oGR + r - I) * 512u, roff, yb);
 #pragma unroll
-        for (int q = 0; q < Q; ++q) st_buf(rrs, (unsigned)(G::oSRL + (r - I) * Q + q) * 512u, roff, ys[q]);
+        for (int q = 0; q < Q; ++q) buf_st(rrs, (unsigned)(G::oSRL + (r - I) * Q + q) * 512u, roff, ys[q]);
       }
     }
     if (!P3 && r == I - 1) {  // the last interior row: what the chunk adds to the previous separator is final
 #pragma unroll
-      for (int k = 0; k < G::NS; ++k) st_buf(rrs, (unsigned)(G::oSLL + k) * 512u, roff, sll[k]);
+      for (int k = 0; k < G::NS; ++k) buf_st(rrs, (unsigned)(G::oSLL + k) * 512u, roff, sll[k]);
 #pragma unroll
-      for (int q = 0; q < Q; ++q) st_buf(rrs, (unsigned)(G::oGL + q) * 512u, roff, gl[q]);
+      for (int q = 0; q < Q; ++q) buf_st(rrs, (unsigned)(G::oGL + q) * 512u, roff, gl[q]);
     }
     __builtin_amdgcn_sched_barrier(0);  // (the scheduler otherwise hoists the later rows' loads and LDS reads over this one)
     if (P3 && NLDS) {  // the row that leaves the window of the forward pass goes to LDS
@@ -383,7 +344,7 @@ __global__ __launch_bounds__(kW * 64, 2) void chunk_kernel(const Problem p, cons
 #pragma unroll
       for (int r = 0; r < C; ++r) {
         const int t = f0 + r;
-        if (t < Tmax) st_buf(ors, (unsigned)t * ldo_bytes, ooff, t < T ? (TOUT)x[r] : (TOUT)0);
+        if (t < Tmax) buf_st(ors, (unsigned)t * ldo_bytes, ooff, t < T ? (TOUT)x[r] : (TOUT)0);
       }
     }
     return;
@@ -409,14 +370,14 @@ __global__ __launch_bounds__(kW * 64, 2) void chunk_kernel(const Problem p, cons
       const bool lv = fl && (w == 0 || (mw != 0 && t >= mw && t < T - mw));
       if (lv) {
         double tau = 1.0;
-        if (VM == MLPG_HIP_VAR_FRAME) tau = tau_of<TIN>(ld_buf<TIN>(vrs, (unsigned)t * ld_bytes + (unsigned)w * win_bytes, loff));
+        if (VM == MLPG_HIP_VAR_FRAME) tau = tau_of<TIN>(buf_ld<TIN>(vrs, (unsigned)t * ld_bytes + (unsigned)w * win_bytes, loff));
         else if (VM == MLPG_HIP_VAR_GLOBAL) tau = tau_g[w];
         double acc_w = 0.0;
 #pragma unroll
         for (int j = -EXT; j <= EXT; ++j) acc_w = __builtin_fma(a.cpad[w][j + EXT], z_at(i + j), acc_w);
         gval = tau * acc_w;
       }
-      if (lane_ok) st_buf(ors, (unsigned)t * ldo_bytes + (unsigned)w * owin_bytes, ooff, (TOUT)gval);
+      if (lane_ok) buf_st(ors, (unsigned)t * ldo_bytes + (unsigned)w * owin_bytes, ooff, (TOUT)gval);
     }
   }
 }

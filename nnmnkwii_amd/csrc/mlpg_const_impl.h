@@ -73,76 +73,10 @@ struct Args {
   StreamMap sm;        // MULTI kernels only: the streams whose static dims sit side by side on the lanes
 };
 
-// MULTI kernels: the stream a merged static-dim index belongs to (at most 4 streams, begin[] ascending, unused entries =
-// INT_MAX) and the dim's columns there (as strip::lane_stream)
-struct LaneStream { int sd, din, dstat, dout; };
-__device__ __forceinline__ LaneStream lane_stream(const StreamMap &sm, int d) {
-  const int s_ = (d >= sm.begin[1]) + (d >= sm.begin[2]) + (d >= sm.begin[3]);
-  auto pick = [&](const int (&v)[4]) { return s_ == 0 ? v[0] : s_ == 1 ? v[1] : s_ == 2 ? v[2] : v[3]; };
-  const int dl = d - pick(sm.begin);
-  return {pick(sm.sd), dl + pick(sm.in_col), dl + pick(sm.stat_col), dl + pick(sm.out_col)};
-}
-
-struct V2 { double x, y; };
-struct M2 { double a, b, c, d; };  // [a b; c d]
-__device__ __forceinline__ V2 mv(const M2 &A, const V2 &v) { return {A.a * v.x + A.b * v.y, A.c * v.x + A.d * v.y}; }
-__device__ __forceinline__ V2 add(const V2 &a, const V2 &b) { return {a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ M2 mm(const M2 &A, const M2 &B) {
-  return {A.a * B.a + A.b * B.c, A.a * B.b + A.b * B.d, A.c * B.a + A.d * B.c, A.c * B.b + A.d * B.d};
-}
-__device__ __forceinline__ double amax4(const M2 &m) {
-  return __builtin_fmax(__builtin_fmax(__builtin_fabs(m.a), __builtin_fabs(m.b)),
-                        __builtin_fmax(__builtin_fabs(m.c), __builtin_fabs(m.d)));
-}
-
-__device__ __forceinline__ double fast_rcp(double d) {
-  double x = __builtin_amdgcn_rcp(d);
-  x = __builtin_fma(__builtin_fma(-d, x, 1.0), x, x);
-  x = __builtin_fma(__builtin_fma(-d, x, 1.0), x, x);
-  return x;
-}
-template <typename T>
-__device__ __forceinline__ double tau_of(T v) { return recip_in_dtype<T>(v); }  // 1/var in the input dtype (_mlpg.py:188)
-
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-// ---- buffer loads / stores: wave-uniform descriptor, row offset in an SGPR, this lane's byte offset in one VGPR ----
-template <typename T>
-__device__ __forceinline__ T ld_row(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff);
-// the same past the CU's L1 (sc0 sc1): rows another wavefront of the workgroup has just written
-template <typename T>
-__device__ __forceinline__ T ld_row_fresh(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff);
-template <>
-__device__ __forceinline__ double ld_row_fresh<double>(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff) {
-  const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, loff, soff, 17);
-  return __longlong_as_double((long long)(((unsigned long long)v.y << 32) | v.x));
-}
-template <>
-__device__ __forceinline__ float ld_row_fresh<float>(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff) {
-  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, loff, soff, 17));
-}
-template <>
-__device__ __forceinline__ double ld_row<double>(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff) {
-  const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, loff, soff, 0);
-  return __longlong_as_double((long long)(((unsigned long long)v.y << 32) | v.x));
-}
-template <>
-__device__ __forceinline__ float ld_row<float>(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff) {
-  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, loff, soff, 0));
-}
-__device__ __forceinline__ void st_row(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff, double v) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  const u32x2 w = {(unsigned)u, (unsigned)(u >> 32)};
-  __builtin_amdgcn_raw_buffer_store_b64(w, rs, loff, soff, 0);
-}
-__device__ __forceinline__ void st_row(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, loff, soff, 0);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base) {
-  // the base must be wave-uniform PROVABLY (a lane-tainted descriptor is wrapped in a waterfall loop per access)
-  const unsigned long long u = (unsigned long long)base;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-  return __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0, 0x7fffffff, 0x00020000);
-}
+// Buffer access, the lane -> stream map of the MULTI kernels, the 2x2 blocks (M2, V2) and the reciprocals: device_prims.h.  1/var is
+// recip_in_dtype here -- the exact reciprocal in the input dtype (_mlpg.py:188), once per dim and launch.
+// Cache policy of the loads that go past the CU's L1 (sc0 sc1): rows another wavefront of the workgroup has just written
+constexpr int kFreshAux = 17;
 
 // ---- the matrix: rows of P for one static dim -------------------------------------------------------------------
 // live(w, t): frame t carries precision for window w -- [0, T) for the static window, [1, T-1) for the dynamic
@@ -182,7 +116,7 @@ __device__ __forceinline__ FacState advance(const FacState &s, const FacRow &r) 
 template <typename TIN, int VM, int NW>
 __device__ __forceinline__ void lane_taus(const Problem &p, int d, int sd, double (&tau)[NW]) {
 #pragma unroll
-  for (int w = 0; w < NW; ++w) tau[w] = VM == MLPG_HIP_VAR_GLOBAL ? tau_of<TIN>(((const TIN *)p.var)[w * sd + d]) : 1.0;
+  for (int w = 0; w < NW; ++w) tau[w] = VM == MLPG_HIP_VAR_GLOBAL ? recip_in_dtype<TIN>(((const TIN *)p.var)[w * sd + d]) : 1.0;
 }
 
 // ---- setup: the T = infinity factor of every dim, until steady ---------------------------------------------------
@@ -272,7 +206,7 @@ __global__ __launch_bounds__(64) void setup_kernel(Problem p, Args a, int M, int
   // below that super-step): the chunk's to the power W
   M2 P = {h1a, h2a, h1b, h2b};
   M2 Q = {1.0, 0.0, 0.0, 1.0};
-  for (int q = 0; q < W; ++q) Q = mm(P, Q);
+  for (int q = 0; q < W; ++q) Q = mul_mm(P, Q);
   const bool small = amax4(Q) < kTol;  // (NaN: false)
   const int ok = __ballot(lane < nd && !small && kfail == 0) == 0ull && i < a.tab_rows && i_s + 2 < M * W;
   if (lane == 0) {
@@ -300,7 +234,7 @@ struct CoefTop {
   __amdgpu_buffer_rsrc_t rows;  // the dim group's table rows (wave-uniform descriptor); lane offset = lane * 8
   unsigned loff;
   int i_s;
-  __device__ __forceinline__ double ld(int j, int q) const { return ld_row<double>(rows, (unsigned)(4 * j + q) * 512u, loff); }
+  __device__ __forceinline__ double ld(int j, int q) const { return buf_ld<double>(rows, (unsigned)(4 * j + q) * 512u, loff); }
   __device__ __forceinline__ Row at(int i) const {
     int j = i < 0 ? 0 : i;
     j = j > i_s ? i_s : j;
@@ -359,7 +293,7 @@ __device__ __forceinline__ void ring_issue(TIN (&ring)[RINGA][BWD ? 1 : NW], int
   t = t < 0 ? 0 : t;  // frames above the utterance's start weigh 0 (chunk 0); never read outside the utterance
 #pragma unroll
   for (int w = 0; w < (BWD ? 1 : NW); ++w)
-    ring[slot][w] = ld_row<TIN>(rs, (unsigned)t * ld_bytes + (unsigned)w * win_bytes, MULTI ? loff + (unsigned)w * wlane : loff);
+    ring[slot][w] = buf_ld<TIN>(rs, (unsigned)t * ld_bytes + (unsigned)w * win_bytes, MULTI ? loff + (unsigned)w * wlane : loff);
 }
 template <typename TIN, bool BWD, int NW, int M, int RING, bool MULTI = false>
 __device__ __forceinline__ void pass1a(TIN (&ring)[RING][BWD ? 1 : NW], __amdgpu_buffer_rsrc_t rs, unsigned loff,
@@ -618,9 +552,9 @@ __global__ __launch_bounds__(W * 64, WPS) void stream_kernel(Problem p, WinSet w
     // padding frames: rows T .. Tmax-1 are zero-filled, a row per wavefront in turn
     if (lane_ok) {
       for (int t = T + wv; t < Tmax; t += W) {
-        if (!BWD) st_row(ors, (unsigned)t * ldo_bytes, ooff, (TOUT)0);
+        if (!BWD) buf_st(ors, (unsigned)t * ldo_bytes, ooff, (TOUT)0);
         else
-          for (int w = 0; w < NW; ++w) st_row(ors, (unsigned)t * ldo_bytes + (unsigned)w * out_win, ooff, (TOUT)0);
+          for (int w = 0; w < NW; ++w) buf_st(ors, (unsigned)t * ldo_bytes + (unsigned)w * out_win, ooff, (TOUT)0);
       }
     }
 #ifndef MLPG_CONST_TIMING
@@ -654,14 +588,14 @@ __global__ __launch_bounds__(W * 64, WPS) void stream_kernel(Problem p, WinSet w
         const int tt = a0c + k;
         if (!lane_ok || (firstc && tt < 0)) return;
         if (!BWD) {
-          st_row(ors, (unsigned)tt * ldo_bytes, ooff, zero_out ? (TOUT)0 : (TOUT)yb);
+          buf_st(ors, (unsigned)tt * ldo_bytes, ooff, zero_out ? (TOUT)0 : (TOUT)yb);
         } else {
 #pragma unroll
           for (int w = 0; w < NW; ++w) {
             double v = tau[w] * (a.wc[w][0] * ya + a.wc[w][1] * yb + a.wc[w][2] * yc);
             if (firstc) v *= live_top(w, tt);
             if (lastc && k == M - 1 && w != 0) v = 0.0;  // the last frame carries no dynamic precision
-            st_row(ors, (unsigned)tt * ldo_bytes + (unsigned)w * out_win, ooff, zero_out ? (TOUT)0 : (TOUT)v);
+            buf_st(ors, (unsigned)tt * ldo_bytes + (unsigned)w * out_win, ooff, zero_out ? (TOUT)0 : (TOUT)v);
           }
         }
       };
@@ -723,7 +657,7 @@ __global__ __launch_bounds__(W * 64, WPS) void stream_kernel(Problem p, WinSet w
         const bool edge_dn = !BWD && !dead && !last && wv == W - 1;
         if (edge_dn) {
 #pragma unroll
-          for (int w = 0; w < NL; ++w) edge[w] = ld_row<TIN>(irs, (unsigned)(a0 + M) * ld_bytes + (unsigned)w * win_bytes, MULTI ? loff + (unsigned)w * wlane : loff);
+          for (int w = 0; w < NL; ++w) edge[w] = buf_ld<TIN>(irs, (unsigned)(a0 + M) * ld_bytes + (unsigned)w * win_bytes, MULTI ? loff + (unsigned)w * wlane : loff);
         }
         double up = 0.0, dn = 0.0;
         if (dead) {
@@ -779,10 +713,10 @@ __global__ __launch_bounds__(W * 64, WPS) void stream_kernel(Problem p, WinSet w
         s_in = {lds.carry[k & 1][0][lane], lds.carry[k & 1][1][lane]};
         for (int c = 0; c < wv; ++c) {
           const M2 Ac = {lds.x[c][2][lane], lds.x[c][3][lane], lds.x[c][4][lane], lds.x[c][5][lane]};
-          s_in = add(V2{lds.x[c][0][lane], lds.x[c][1][lane]}, mv(Ac, s_in));
+          s_in = add(V2{lds.x[c][0][lane], lds.x[c][1][lane]}, mul_mv(Ac, s_in));
         }
         if (wv == W - 1) {  // ... and the next super-step's
-          const V2 sn = add(g2, mv(A2, s_in));
+          const V2 sn = add(g2, mul_mv(A2, s_in));
           lds.carry[(k + 1) & 1][0][lane] = sn.x;
           lds.carry[(k + 1) & 1][1][lane] = sn.y;
         }
@@ -813,14 +747,14 @@ __global__ __launch_bounds__(W * 64, WPS) void stream_kernel(Problem p, WinSet w
           for (int c = W - 1; c >= 0; --c) {
             if (c == wv) { tl = Ehat; Bs = Prun; }
             const M2 Bc = {lds.x[c][2][lane], lds.x[c][3][lane], lds.x[c][4][lane], lds.x[c][5][lane]};
-            Ehat = add(V2{lds.x[c][0][lane], lds.x[c][1][lane]}, mv(Bc, Ehat));
-            Prun = mm(Bc, Prun);
+            Ehat = add(V2{lds.x[c][0][lane], lds.x[c][1][lane]}, mul_mv(Bc, Ehat));
+            Prun = mul_mm(Bc, Prun);
           }
         }
         CST_TICK(7);
         // ---- the chunk parked one super-step ago: out, with what came up from this super-step
         if (parked) {
-          const V2 t_p = add(tl_p, mv(Bs_p, Ehat));
+          const V2 t_p = add(tl_p, mul_mv(Bs_p, Ehat));
           auto from_lds = [&](int kk) __attribute__((always_inline)) { return lds.park[slot][kk][lane]; };
           if (steady_p) rows_out(from_lds, cc, t_p, a0_p, first_p, false, sx_p);
           else rows_out(from_lds, ct, t_p, a0_p, first_p, false, sx_p);
@@ -872,7 +806,7 @@ __global__ __launch_bounds__(W * 64, WPS) void stream_kernel(Problem p, WinSet w
         const bool edge_dn = !BWD && !dead && !last && wv == W - 1;
         if (edge_dn) {
 #pragma unroll
-          for (int w = 0; w < NL; ++w) edge[w] = ld_row<TIN>(irs, (unsigned)(a0 + M) * ld_bytes + (unsigned)w * win_bytes, MULTI ? loff + (unsigned)w * wlane : loff);
+          for (int w = 0; w < NL; ++w) edge[w] = buf_ld<TIN>(irs, (unsigned)(a0 + M) * ld_bytes + (unsigned)w * win_bytes, MULTI ? loff + (unsigned)w * wlane : loff);
         }
         double up = 0.0, dn = 0.0;
         if (dead) {
@@ -920,10 +854,10 @@ __global__ __launch_bounds__(W * 64, WPS) void stream_kernel(Problem p, WinSet w
         V2 s_in = {lds.carry[k & 1][0][lane], lds.carry[k & 1][1][lane]};
         for (int c = 0; c < wv; ++c) {
           const M2 Ac = {lds.x[c][2][lane], lds.x[c][3][lane], lds.x[c][4][lane], lds.x[c][5][lane]};
-          s_in = add(V2{lds.x[c][0][lane], lds.x[c][1][lane]}, mv(Ac, s_in));
+          s_in = add(V2{lds.x[c][0][lane], lds.x[c][1][lane]}, mul_mv(Ac, s_in));
         }
         if (wv == W - 1) {
-          const V2 sn = add(g2, mv(A2, s_in));
+          const V2 sn = add(g2, mul_mv(A2, s_in));
           lds.carry[(k + 1) & 1][0][lane] = sn.x;
           lds.carry[(k + 1) & 1][1][lane] = sn.y;
         }
@@ -940,7 +874,7 @@ __global__ __launch_bounds__(W * 64, WPS) void stream_kernel(Problem p, WinSet w
               dm2 = dm1;
               dm1 = dl;
               const int t = a0 + i;
-              if (lane_ok && (!first || t >= 0)) st_row(prs, (unsigned)t * ldo_bytes, ooff, (TOUT)((z[i] + dl) * r.dinv));
+              if (lane_ok && (!first || t >= 0)) buf_st(prs, (unsigned)t * ldo_bytes, ooff, (TOUT)((z[i] + dl) * r.dinv));
             }
           };
           if (steady) park(cc); else park(ct);
@@ -966,10 +900,10 @@ __global__ __launch_bounds__(W * 64, WPS) void stream_kernel(Problem p, WinSet w
           for (int i = 0; i < M; ++i) {
             int t = a0 + i;
             t = t < 0 ? 0 : t;
-            z[i] = (double)ld_row_fresh<TOUT>(prs, (unsigned)t * ldo_bytes, ooff);
+            z[i] = (double)buf_ld<TOUT, kFreshAux>(prs, (unsigned)t * ldo_bytes, ooff);
             if (first && a0 + i < 0) z[i] = 0.0;
           }
-          if (BWD && a0 >= 1) vm1 = (double)ld_row_fresh<TOUT>(prs, (unsigned)(a0 - 1) * ldo_bytes, ooff);
+          if (BWD && a0 >= 1) vm1 = (double)buf_ld<TOUT, kFreshAux>(prs, (unsigned)(a0 - 1) * ldo_bytes, ooff);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every parked row is in registers before anybody overwrites one
         // local backward recurrence over the parked (already scaled) values
@@ -1007,7 +941,7 @@ __global__ __launch_bounds__(W * 64, WPS) void stream_kernel(Problem p, WinSet w
         for (int c = W - 1; c >= 0; --c) {
           if (c == wv) t_in = top;
           const M2 Bc = {lds.x[c][2][lane], lds.x[c][3][lane], lds.x[c][4][lane], lds.x[c][5][lane]};
-          top = add(V2{lds.x[c][0][lane], lds.x[c][1][lane]}, mv(Bc, top));
+          top = add(V2{lds.x[c][0][lane], lds.x[c][1][lane]}, mul_mv(Bc, top));
         }
         if (wv == 0) { lds.carry[k & 1][0][lane] = top.x; lds.carry[k & 1][1][lane] = top.y; }
         if (!dead) {

@@ -24,7 +24,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "device_prims.h"
 
 namespace mlpg {
 
@@ -52,20 +52,10 @@ struct Args {
 };
 
 typedef __attribute__((ext_vector_type(2))) float f32x2;
-// Raw buffer access: address = base + soff (scalar: the frame's row) + loff (per lane: the dim).  The hardware checks loff -- not soff --
-// against the descriptor's 2^31 - 1 bytes; the kernels use that as their mask: with loff = 0x80000000 a load returns 0 and a store is
-// dropped, without a branch and without a select on the data (rows_fit_buffer keeps every real offset below 2^31).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base) {
-  const unsigned long long u = (unsigned long long)base;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-  return __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0, 0x7fffffff, 0x00020000);
-}
-__device__ __forceinline__ float ld_f32(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff) {
-  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, loff, soff, 0));
-}
-__device__ __forceinline__ void st_f32(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, loff, soff, 0);
-}
+// Raw buffer access (device_prims.h: make_rsrc, buf_ld, buf_st): address = base + soff (scalar: the frame's row) + loff (per lane: the
+// dim).  The hardware checks loff -- not soff -- against the descriptor's 2^31 - 1 bytes; the kernels use that as their mask: with
+// loff = 0x80000000 a load returns 0 and a store is dropped, without a branch and without a select on the data (rows_fit_buffer keeps
+// every real offset below 2^31).
 
 __device__ __forceinline__ double wave_sum(double v) {  // lanes added in a fixed order
 #pragma unroll
@@ -144,7 +134,7 @@ __device__ __forceinline__ void fir_tiles(const Problem &p, const Args &a, const
     for (int s = 0; s < NF; ++s) {
       const int t = f_first + s;
       const int tc = t < 0 ? 0 : (t >= T ? T - 1 : t);
-      bb[s] = ld_f32(irs, (unsigned)tc * ldi_bytes, (unsigned)t < (unsigned)T ? loff : kDrop);  // (a read behind the buffer's end returns 0)
+      bb[s] = buf_ld<float>(irs, (unsigned)tc * ldi_bytes, (unsigned)t < (unsigned)T ? loff : kDrop);  // (a read behind the buffer's end returns 0)
     }
     __builtin_amdgcn_sched_barrier(0);
   } else {
@@ -166,7 +156,7 @@ __device__ __forceinline__ void fir_tiles(const Problem &p, const Args &a, const
           for (int w = 0; w < kMaxNw; ++w) {
             // the window's mask and the utterance's ends through the offset: a read behind the buffer's end returns 0
             const bool lv = (unsigned)(t - lo[w]) < span[w];
-            mu[(q + 1) & 1][s][w] = ld_f32(irs, (unsigned)tc * ldi_bytes + (unsigned)(w < nw ? w : 0) * win_bytes, lv ? loff : kDrop);
+            mu[(q + 1) & 1][s][w] = buf_ld<float>(irs, (unsigned)tc * ldi_bytes + (unsigned)(w < nw ? w : 0) * win_bytes, lv ? loff : kDrop);
           }
         }
       }
@@ -236,7 +226,7 @@ __device__ __forceinline__ void fir_tiles(const Problem &p, const Args &a, const
 #pragma unroll
     for (int r = 0; r < TT; ++r) {
       const int t = t0e + r;
-      tg[r] = ld_f32(trs, (unsigned)(t < T ? t : 0) * win_bytes, (unsigned)(t - EW) < (unsigned)(T - 2 * EW) ? soff_ok : kDrop);
+      tg[r] = buf_ld<float>(trs, (unsigned)(t < T ? t : 0) * win_bytes, (unsigned)(t - EW) < (unsigned)(T - 2 * EW) ? soff_ok : kDrop);
     }
     __builtin_amdgcn_sched_barrier(0);
     int t0f = t0e;  // (opaque again: else the 32 row masks of the loads above are kept in scalar registers for the stores, and spill)
@@ -249,8 +239,8 @@ __device__ __forceinline__ void fir_tiles(const Problem &p, const Args &a, const
       const unsigned so = mine ? soff_ok : kDrop;
       const float e = out[r] - tg[r];
       const float em = so == kDrop ? 0.0f : e;
-      st_f32(ors, (unsigned)(t < T ? t : 0) * ldo_bytes, mine ? yoff : kDrop, out[r]);
-      st_f32(drs, (unsigned)(t < T ? t : 0) * win_bytes, so, a.scale * e);
+      buf_st(ors, (unsigned)(t < T ? t : 0) * ldo_bytes, mine ? yoff : kDrop, out[r]);
+      buf_st(drs, (unsigned)(t < T ? t : 0) * win_bytes, so, a.scale * e);
       ls = __builtin_fmaf(em, em, ls);
       if (r % 4 == 3) __builtin_amdgcn_sched_barrier(0);
     }
@@ -260,7 +250,7 @@ __device__ __forceinline__ void fir_tiles(const Problem &p, const Args &a, const
 #pragma unroll
     for (int r = 0; r < TT; ++r) {
       const int t = t0e + r;
-      st_f32(ors, (unsigned)(t < T ? t : 0) * ldo_bytes, (unsigned)(t - EW) < (unsigned)(T - 2 * EW) ? soff_ok : kDrop, out[r]);
+      buf_st(ors, (unsigned)(t < T ? t : 0) * ldo_bytes, (unsigned)(t - EW) < (unsigned)(T - 2 * EW) ? soff_ok : kDrop, out[r]);
       if (r % 8 == 7) __builtin_amdgcn_sched_barrier(0);  // (else every offset is computed up front and the scalars spill)
     }
   } else {
@@ -278,7 +268,7 @@ __device__ __forceinline__ void fir_tiles(const Problem &p, const Args &a, const
           if (w == 0 && k != 0) continue;
           gsum = __builtin_fmaf(cw[w][k + EXT], out[r + EXT + k], gsum);
         }
-        st_f32(ors, (unsigned)(t < T ? t : 0) * ldo_bytes + (unsigned)(w < nw ? w : 0) * win_bytes, (mine && w < nw) ? soff_ok : kDrop, lv ? gsum : 0.0f);
+        buf_st(ors, (unsigned)(t < T ? t : 0) * ldo_bytes + (unsigned)(w < nw ? w : 0) * win_bytes, (mine && w < nw) ? soff_ok : kDrop, lv ? gsum : 0.0f);
       }
       if (r % 4 == 3) __builtin_amdgcn_sched_barrier(0);  // (else every offset is computed up front and the scalars spill)
     }
@@ -351,7 +341,7 @@ __device__ __forceinline__ void fir_tiles_shared(const Problem &p, const Args &a
       for (int s = 0; s < RPW; ++s) {
         const int t = f_first + s;
         const int tc = t < 0 ? 0 : (t >= T ? T - 1 : t);
-        v[s] = ld_f32(irs, (unsigned)tc * ldi_bytes, (unsigned)t < (unsigned)T ? loff : kDrop);
+        v[s] = buf_ld<float>(irs, (unsigned)tc * ldi_bytes, (unsigned)t < (unsigned)T ? loff : kDrop);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -374,7 +364,7 @@ __device__ __forceinline__ void fir_tiles_shared(const Problem &p, const Args &a
 #pragma unroll
             for (int w = 0; w < kMaxNw; ++w) {
               const bool lv = (unsigned)(t - lo[w]) < span[w];
-              mu[(q + 1) & 1][s][w] = ld_f32(irs, (unsigned)tc * ldi_bytes + (unsigned)(w < nw ? w : 0) * win_bytes, lv ? loff : kDrop);
+              mu[(q + 1) & 1][s][w] = buf_ld<float>(irs, (unsigned)tc * ldi_bytes + (unsigned)(w < nw ? w : 0) * win_bytes, lv ? loff : kDrop);
             }
           }
         }
@@ -443,7 +433,7 @@ __device__ __forceinline__ void fir_tiles_shared(const Problem &p, const Args &a
 #pragma unroll
     for (int r = 0; r < TT; ++r) {
       const int t = t0e + r;
-      tg[r] = ld_f32(trs, (unsigned)(t < T ? t : 0) * win_bytes, (unsigned)(t - EW) < (unsigned)(T - 2 * EW) ? soff_ok : kDrop);
+      tg[r] = buf_ld<float>(trs, (unsigned)(t < T ? t : 0) * win_bytes, (unsigned)(t - EW) < (unsigned)(T - 2 * EW) ? soff_ok : kDrop);
     }
     __builtin_amdgcn_sched_barrier(0);
     int t0f = t0e;
@@ -456,8 +446,8 @@ __device__ __forceinline__ void fir_tiles_shared(const Problem &p, const Args &a
       const unsigned so = mine ? soff_ok : kDrop;
       const float e = out[r] - tg[r];
       const float em = so == kDrop ? 0.0f : e;
-      st_f32(ors, (unsigned)(t < T ? t : 0) * ldo_bytes, mine ? yoff : kDrop, out[r]);
-      st_f32(drs, (unsigned)(t < T ? t : 0) * win_bytes, so, a.scale * e);
+      buf_st(ors, (unsigned)(t < T ? t : 0) * ldo_bytes, mine ? yoff : kDrop, out[r]);
+      buf_st(drs, (unsigned)(t < T ? t : 0) * win_bytes, so, a.scale * e);
       ls = __builtin_fmaf(em, em, ls);
       if (r % 4 == 3) __builtin_amdgcn_sched_barrier(0);
     }
@@ -467,7 +457,7 @@ __device__ __forceinline__ void fir_tiles_shared(const Problem &p, const Args &a
 #pragma unroll
     for (int r = 0; r < TT; ++r) {
       const int t = t0e + r;
-      st_f32(ors, (unsigned)(t < T ? t : 0) * ldo_bytes, (unsigned)(t - EW) < (unsigned)(T - 2 * EW) ? soff_ok : kDrop, out[r]);
+      buf_st(ors, (unsigned)(t < T ? t : 0) * ldo_bytes, (unsigned)(t - EW) < (unsigned)(T - 2 * EW) ? soff_ok : kDrop, out[r]);
       if (r % 8 == 7) __builtin_amdgcn_sched_barrier(0);  // (else every offset is computed up front and the scalars spill)
     }
   } else {
@@ -485,7 +475,7 @@ __device__ __forceinline__ void fir_tiles_shared(const Problem &p, const Args &a
           if (w == 0 && k != 0) continue;
           gsum = __builtin_fmaf(cw[w][k + EXT], out[r + EXT + k], gsum);
         }
-        st_f32(ors, (unsigned)(t < T ? t : 0) * ldo_bytes + (unsigned)(w < nw ? w : 0) * win_bytes, (mine && w < nw) ? soff_ok : kDrop, lv ? gsum : 0.0f);
+        buf_st(ors, (unsigned)(t < T ? t : 0) * ldo_bytes + (unsigned)(w < nw ? w : 0) * win_bytes, (mine && w < nw) ? soff_ok : kDrop, lv ? gsum : 0.0f);
       }
       if (r % 4 == 3) __builtin_amdgcn_sched_barrier(0);  // (else every offset is computed up front and the scalars spill)
     }
@@ -546,7 +536,7 @@ __device__ __forceinline__ void fir_ends(const Problem &p, const Args &a, const 
     const int j = i * NWV + wv;
     const int fi = frame(j < NBE ? j : NBE - 1);
     if (BWD) {
-      mu[i][0] = ld_f32(irs, (unsigned)fi * ldi_bytes, loff);
+      mu[i][0] = buf_ld<float>(irs, (unsigned)fi * ldi_bytes, loff);
     } else {
 #pragma unroll
       for (int w = 0; w < kMaxNw; ++w) {
@@ -557,7 +547,7 @@ __device__ __forceinline__ void fir_ends(const Problem &p, const Args &a, const 
           const int tc = t < 0 ? 0 : (t >= T ? T - 1 : t);
           const bool lv = w < nw && t >= 0 && t < T && (w == 0 || (mw != 0 && t >= mw && t < T - mw));
           mu[i][w == 0 ? 0 : 1 + (w - 1) * (2 * EXT + 1) + k + EXT] =
-              ld_f32(irs, (unsigned)tc * ldi_bytes + (unsigned)(w < nw ? w : 0) * win_bytes, lv ? loff : kDrop);
+              buf_ld<float>(irs, (unsigned)tc * ldi_bytes + (unsigned)(w < nw ? w : 0) * win_bytes, lv ? loff : kDrop);
         }
       }
     }

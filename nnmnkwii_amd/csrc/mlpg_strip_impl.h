@@ -148,6 +148,7 @@ constexpr int kCtrlLine = 32;
                                 // (profiles/r05_strip_stores_ab.txt): forward f64 +1.9 %, backward f32 +5.5 %.  (Round 3 measured the same gain and
                                 // its notes called it shipped, but the default stayed 0 until round 5.)
 #endif
+constexpr int kRowStoreAux = MLPG_STRIP_NT_STORES ? 2 : 0;  // cache-policy immediate of those rows' buffer stores (2: nt)
 #ifndef MLPG_STRIP_RING_F64
 #define MLPG_STRIP_RING_F64 6
 #endif
@@ -245,22 +246,6 @@ __device__ __forceinline__ void ticket_item(const Args &a, int tk, int lst, int 
   }
 }
 
-// MULTI kernels: the stream a merged static-dim index belongs to (at most 4 streams, begin[] ascending, unused
-// entries = INT_MAX) and the dim's columns there
-struct LaneStream { int sd, din, dstat, dout, dvar; };  // dvar: the dim's window-0 column in a global (D,) variance vector
-// transposed form (StreamMap::tr_u): merged index d = u * tr_nd + dim of utterance b0 + u; the columns carry the utterance's offset
-__device__ __forceinline__ LaneStream lane_stream_tr(const StreamMap &sm, int d) {
-  const int u = d / sm.tr_nd, dl = d - u * sm.tr_nd;
-  return {sm.sd[0], u * sm.tr_in + sm.in_col[0] + dl, u * sm.tr_stat + sm.stat_col[0] + dl, u * sm.tr_out + sm.out_col[0] + dl,
-          sm.in_col[0] + dl};
-}
-__device__ __forceinline__ LaneStream lane_stream(const StreamMap &sm, int d) {
-  const int s_ = (d >= sm.begin[1]) + (d >= sm.begin[2]) + (d >= sm.begin[3]);
-  auto pick = [&](const int (&v)[4]) { return s_ == 0 ? v[0] : s_ == 1 ? v[1] : s_ == 2 ? v[2] : v[3]; };
-  const int dl = d - pick(sm.begin);
-  return {pick(sm.sd), dl + pick(sm.in_col), dl + pick(sm.stat_col), dl + pick(sm.out_col), dl + pick(sm.in_col)};
-}
-
 constexpr size_t kLdsStage = (size_t)kStage * kRec * 64 * 8;     // level-3 staging; its head doubles as the level-1 records
 constexpr size_t kLdsPark = (size_t)kPark * 64 * 8;
 constexpr size_t kLdsFac = (size_t)(kW - 1) * kFac * 64 * 8;
@@ -270,65 +255,13 @@ constexpr size_t kLdsBytes = kLdsStage + kLdsPark + kLdsFac + kLdsU + kLdsMisc;
 static_assert(kW * kRec <= kStage * kRec, "level-1 records must fit the staging area");
 static_assert(kLdsBytes <= 160 * 1024 / MLPG_STRIP_WGS, "MLPG_STRIP_WGS workgroups per CU must fit the 160 KB of LDS");
 
-__device__ __forceinline__ double fast_rcp(double d) {
-  double x = __builtin_amdgcn_rcp(d);
-  x = __builtin_fma(__builtin_fma(-d, x, 1.0), x, x);
-  x = __builtin_fma(__builtin_fma(-d, x, 1.0), x, x);
-  return x;
-}
-template <typename T>
-__device__ __forceinline__ double tau_of(T v);
-template <>
-__device__ __forceinline__ double tau_of<float>(float v) {
-  return (double)__fdiv_rn(1.0f, v);  // float32 reciprocal, as _mlpg.py:188
-}
-template <>
-__device__ __forceinline__ double tau_of<double>(double v) {
-  return fast_rcp(v);
-}
-
-// ---- 2x2 blocks, one per lane ---------------------------------------------------------------
-struct S2 { double a, b, c; };     // symmetric [a b; b c]
-struct M2 { double a, b, c, d; };  // full      [a b; c d]
-struct V2 { double x, y; };
-
+// strip's inverse of a symmetric 2x2 pivot block (S2, M2, V2 and their algebra: device_prims.h); `bad` collects failing pivots
 __device__ __forceinline__ S2 sym_inv(const S2 &E, bool &bad) {
   const double det = E.a * E.c - E.b * E.b;
   bad |= (E.a <= 0.0) | (det <= 0.0) | !(det == det);
   const double idet = fast_rcp(det);
   return {E.c * idet, -E.b * idet, E.a * idet};
 }
-__device__ __forceinline__ M2 mul_ms(const M2 &L, const S2 &S) {  // L S
-  return {L.a * S.a + L.b * S.b, L.a * S.b + L.b * S.c, L.c * S.a + L.d * S.b, L.c * S.b + L.d * S.c};
-}
-__device__ __forceinline__ M2 mul_sm(const S2 &S, const M2 &V) {  // S V
-  return {S.a * V.a + S.b * V.c, S.a * V.b + S.b * V.d, S.b * V.a + S.c * V.c, S.b * V.b + S.c * V.d};
-}
-__device__ __forceinline__ M2 mul_smt(const S2 &S, const M2 &V) {  // S V^T
-  return {S.a * V.a + S.b * V.b, S.a * V.c + S.b * V.d, S.b * V.a + S.c * V.b, S.b * V.c + S.c * V.d};
-}
-__device__ __forceinline__ double amax4(const M2 &m) {  // twice this bounds the block's 2-norm
-  return __builtin_fmax(__builtin_fmax(__builtin_fabs(m.a), __builtin_fabs(m.b)),
-                        __builtin_fmax(__builtin_fabs(m.c), __builtin_fabs(m.d)));
-}
-__device__ __forceinline__ M2 mul_mm(const M2 &A, const M2 &B) {
-  return {A.a * B.a + A.b * B.c, A.a * B.b + A.b * B.d, A.c * B.a + A.d * B.c, A.c * B.b + A.d * B.d};
-}
-__device__ __forceinline__ S2 mul_mmt_sym(const M2 &A, const M2 &B) {  // A B^T, symmetric by construction
-  return {A.a * B.a + A.b * B.b, A.a * B.c + A.b * B.d, A.c * B.c + A.d * B.d};
-}
-__device__ __forceinline__ S2 mul_mtm_sym(const M2 &A, const M2 &B) {  // A^T B, symmetric by construction
-  return {A.a * B.a + A.c * B.c, A.a * B.b + A.c * B.d, A.b * B.b + A.d * B.d};
-}
-__device__ __forceinline__ V2 mul_mv(const M2 &A, const V2 &v) { return {A.a * v.x + A.b * v.y, A.c * v.x + A.d * v.y}; }
-__device__ __forceinline__ V2 mul_mtv(const M2 &A, const V2 &v) { return {A.a * v.x + A.c * v.y, A.b * v.x + A.d * v.y}; }
-__device__ __forceinline__ V2 mul_sv(const S2 &S, const V2 &v) { return {S.a * v.x + S.b * v.y, S.b * v.x + S.c * v.y}; }
-__device__ __forceinline__ S2 sub(const S2 &A, const S2 &B) { return {A.a - B.a, A.b - B.b, A.c - B.c}; }
-__device__ __forceinline__ S2 add(const S2 &A, const S2 &B) { return {A.a + B.a, A.b + B.b, A.c + B.c}; }
-__device__ __forceinline__ V2 sub(const V2 &A, const V2 &B) { return {A.x - B.x, A.y - B.y}; }
-__device__ __forceinline__ V2 add(const V2 &A, const V2 &B) { return {A.x + B.x, A.y + B.y}; }
-__device__ __forceinline__ M2 neg(const M2 &A) { return {-A.a, -A.b, -A.c, -A.d}; }
-__device__ __forceinline__ M2 transpose(const M2 &A) { return {A.a, A.c, A.b, A.d}; }
 
 // agent-scope (sc1, write-through / L1-bypassing) 8-byte accesses for the records
 __device__ __forceinline__ void st_agent(double *p, double v) {
@@ -352,51 +285,8 @@ constexpr int kNB = kM == 16 ? 6 : 2;  // batches per window (even: every window
 constexpr int kHB = (kM + 2) / kNB;   // frames per batch
 static_assert(kHB * kNB == kM + 2, "batches must tile the 18 frames");
 
-// Loads go through buffer descriptors: a wave-uniform descriptor (the utterance's rows from the dim group's first
-// column on), the row/window offset in an SGPR (soffset) and this lane's 32-bit byte offset in ONE VGPR -- no
-// per-load 64-bit address arithmetic and no address registers (global_load with 64-bit VGPR addresses costs two VALU
-// instructions and a register pair per load, which is what drove this kernel into scratch).
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-template <typename TIN>
-__device__ __forceinline__ TIN ld_row(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff);
-template <>
-__device__ __forceinline__ double ld_row<double>(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff) {
-  const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, loff, soff, 0);
-  return __longlong_as_double((long long)(((unsigned long long)v.y << 32) | v.x));
-}
-template <>
-__device__ __forceinline__ float ld_row<float>(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff) {
-  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, loff, soff, 0));
-}
-// the backward's grad_out rows (round 3 measured the `nt` cache policy for them: 2 % slower)
-template <typename TIN>
-__device__ __forceinline__ TIN ld_row_g(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff);
-template <>
-__device__ __forceinline__ double ld_row_g<double>(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff) {
-  const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, loff, soff, 0);
-  return __longlong_as_double((long long)(((unsigned long long)v.y << 32) | v.x));
-}
-template <>
-__device__ __forceinline__ float ld_row_g<float>(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff) {
-  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, loff, soff, 0));
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base) {
-  // the base must be wave-uniform PROVABLY (a lane-tainted descriptor is wrapped in a waterfall loop per load)
-  const unsigned long long u = (unsigned long long)base;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-  return __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0, 0x7fffffff, 0x00020000);
-}
-
-// row stores through a buffer descriptor (backward epilogue): scalar row/window offset + one lane offset, no 64-bit
-// address arithmetic per store
-__device__ __forceinline__ void st_row(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff, double v) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  const u32x2 w = {(unsigned)u, (unsigned)(u >> 32)};
-  __builtin_amdgcn_raw_buffer_store_b64(w, rs, loff, soff, MLPG_STRIP_NT_STORES ? 2 : 0);
-}
-__device__ __forceinline__ void st_row(__amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned loff, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, loff, soff, MLPG_STRIP_NT_STORES ? 2 : 0);
-}
+// Rows are loaded and stored through buffer descriptors (device_prims.h: make_rsrc, buf_ld, buf_st): scalar row/window offset + one
+// lane offset, no 64-bit address arithmetic per access; the stores carry kRowStoreAux.
 
 // Window coefficients straight from the kernel-argument segment, as scalar loads PLACED by the caller (backward
 // kernels, round 5).  The arguments by value are preloaded into scalar registers at kernel entry and live from there to
@@ -461,8 +351,8 @@ __device__ __forceinline__ void load_batch(TIN (&rv)[kHB], TIN (&rm)[kHB], __amd
     int t = f0 + H * kHB + q - 1;
     if (EDGE) t = t < lo ? lo : (t >= hi ? hi - 1 : t);
     const unsigned soff = (unsigned)t * ldi_bytes + woff;
-    if (VM == MLPG_HIP_VAR_FRAME) rv[q] = ld_row<TIN>(vrs, soff, loff);
-    if (!BWD) rm[q] = ld_row<TIN>(mrs, soff, loff);
+    if (VM == MLPG_HIP_VAR_FRAME) rv[q] = buf_ld<TIN>(vrs, soff, loff);
+    if (!BWD) rm[q] = buf_ld<TIN>(mrs, soff, loff);
   }
 }
 
@@ -552,7 +442,8 @@ __device__ __forceinline__ void assemble(__amdgpu_buffer_rsrc_t mrs, __amdgpu_bu
     for (int i = 0; i < kM; ++i) {
       int t = f0 + i;
       if (EDGE) t = t >= T ? T - 1 : t;
-      rhs[i] = (double)ld_row_g<TIN>(grs, (unsigned)t * (unsigned)ldg * (unsigned)sizeof(TIN), loff);  // rows >= T are reset below
+      // grad_out rows with the default cache policy (round 3 measured `nt` for them: 2 % slower)
+      rhs[i] = (double)buf_ld<TIN>(grs, (unsigned)t * (unsigned)ldg * (unsigned)sizeof(TIN), loff);  // rows >= T are reset below
     }
   }
   for (int w = 0; w < nw; ++w) {
@@ -769,8 +660,8 @@ __device__ __forceinline__ bool assemble_eliminate(__amdgpu_buffer_rsrc_t mrs, _
       // lane offset; otherwise it is wave-uniform and rides in the scalar offset
       const unsigned soff = MULTI ? frame_off : frame_off + (unsigned)w * win_bytes;
       const unsigned voff = MULTI ? loff + (unsigned)w * win_bytes : loff;
-      if (VM == MLPG_HIP_VAR_FRAME) v[w] = ld_row<TIN>(vrs, soff, voff);
-      if (!BWD) m[w] = ld_row<TIN>(mrs, soff, voff);
+      if (VM == MLPG_HIP_VAR_FRAME) v[w] = buf_ld<TIN>(vrs, soff, voff);
+      if (!BWD) m[w] = buf_ld<TIN>(mrs, soff, voff);
     }
   };
   auto accumulate_frame = [&](const TIN (&v)[NW], const TIN (&m)[NW], const int i) __attribute__((always_inline)) {
@@ -932,7 +823,7 @@ __device__ __forceinline__ bool assemble_eliminate(__amdgpu_buffer_rsrc_t mrs, _
     for (int i = 0; i < kM; ++i) {
       int t = f0 + i;
       if (EDGE) t = t >= T ? T - 1 : t;
-      rhs[i] = (double)ld_row_g<TIN>(grs, (unsigned)t * (unsigned)ldg * (unsigned)sizeof(TIN), loff);  // rows >= T are reset by fix_row
+      rhs[i] = (double)buf_ld<TIN>(grs, (unsigned)t * (unsigned)ldg * (unsigned)sizeof(TIN), loff);  // rows >= T are reset by fix_row
     }
   }
   __builtin_amdgcn_sched_barrier(0);
@@ -1149,7 +1040,7 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
     const unsigned ldi_b = (unsigned)ldi * (unsigned)sizeof(TIN), win_b = (unsigned)sd * (unsigned)sizeof(TIN);
 #pragma unroll
     for (int w = 0; w < 3; ++w) {
-      v[w] = ld_row<TIN>(vrs, (unsigned)t * ldi_b + (unsigned)w * win_b, loff);  // (only the NW3 kernel comes here)
+      v[w] = buf_ld<TIN>(vrs, (unsigned)t * ldi_b + (unsigned)w * win_b, loff);  // (only the NW3 kernel comes here)
     }
   };
   auto early_issue = [&]() __attribute__((always_inline)) {
@@ -1287,7 +1178,7 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
 #pragma unroll
     for (int i = 0; i < kM; ++i) {
       const int t = f0 + i;
-      if (t < Tmax) st_row(ors_f, (unsigned)t * ldo_b, ooff_f, (t < T && !zero_out) ? (TOUT)rhs[i] : (TOUT)0);
+      if (t < Tmax) buf_st<kRowStoreAux>(ors_f, (unsigned)t * ldo_b, ooff_f, (t < T && !zero_out) ? (TOUT)rhs[i] : (TOUT)0);
     }
 #else
 #pragma unroll
@@ -1315,7 +1206,7 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
       for (int i = -1; i < kM; ++i) {
         int t = f0 + i;
         t = t < 0 ? 0 : (t >= T ? T - 1 : t);  // in bounds; a row that is not live is not used
-        v[i + 1] = ld_row<TIN>(vrs, (unsigned)t * ldi_bytes + (unsigned)w * win_bytes, loff);
+        v[i + 1] = buf_ld<TIN>(vrs, (unsigned)t * ldi_bytes + (unsigned)w * win_bytes, loff);
       }
     };
     auto emit_w = [&](const TIN (&v)[kM + 1], const int w) __attribute__((always_inline)) {
@@ -1378,7 +1269,7 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
         if (MLPG_STRIP_BWD_BUFSTORE) asm volatile("" : "+s"(row_off));  // (not one of 17 loop invariants held in scalar registers)
         auto put = [&](const int w, const TOUT val) __attribute__((always_inline)) {
 #if MLPG_STRIP_BWD_BUFSTORE
-          st_row(ors_e, row_off + (unsigned)w * (unsigned)sd * (unsigned)sizeof(TOUT), ooff_e, val);
+          buf_st<kRowStoreAux>(ors_e, row_off + (unsigned)w * (unsigned)sd * (unsigned)sizeof(TOUT), ooff_e, val);
           return;
 #endif
 #if MLPG_STRIP_NT_STORES

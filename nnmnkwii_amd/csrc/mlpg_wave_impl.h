@@ -66,26 +66,7 @@ namespace {
 constexpr int kG = 4;     // systems (wavefronts) per workgroup
 constexpr int kSkew = 1;  // padding slot per chunk in the register-staged tile layout
 
-// 1/d to ~1 ulp: hardware seed + two Newton steps (an IEEE-exact f64 divide is ~2x the
-// instructions; the difference, 1e-16 relative, is far below every tolerance on this path).
-__device__ __forceinline__ double fast_rcp(double d) {
-  double x = __builtin_amdgcn_rcp(d);
-  x = __builtin_fma(__builtin_fma(-d, x, 1.0), x, x);
-  x = __builtin_fma(__builtin_fma(-d, x, 1.0), x, x);
-  return x;
-}
-
-// tau = 1/var: float32 inputs keep the reference's float32 reciprocal (_mlpg.py:188)
-template <typename T>
-__device__ __forceinline__ double tau_of(T v);
-template <>
-__device__ __forceinline__ double tau_of<float>(float v) {
-  return (double)__fdiv_rn(1.0f, v);
-}
-template <>
-__device__ __forceinline__ double tau_of<double>(double v) {
-  return fast_rcp(v);
-}
+// 1/d (fast_rcp) and tau = 1/var (tau_of): device_prims.h
 
 constexpr int log2i(int m) { return m == 4 ? 2 : m == 8 ? 3 : m == 16 ? 4 : 5; }
 
