@@ -5,15 +5,15 @@
 //                                    every load/store instruction moves one contiguous run of
 //                                    sd elements of a frame, no LDS transposition)
 //   wavefront = chunk of M = 16 consecutive frames of one utterance
-//   workgroup = strip of W = 4 consecutive chunks (64 frames); two workgroups per CU
+//   workgroup = strip of W = 4 consecutive chunks (64 frames); MLPG_STRIP_WGS = 2 workgroups per CU
 //   an utterance of T frames is ceil(T / 64) strips that run on different CUs.
 // Windows must have extents l, u <= 1 (pentadiagonal P), any T.
 //
 // The solve is a three-level substructured LDL^T (tools/strip_model.py is the executable
 // specification, pinned against the oracle by tests/test_strip_model.py):
 //   level 1 (wavefront, registers): assemble the chunk's rows of P = sum_w W_w^T diag(tau_w) W_w
-//     and b from the frames f0-1 .. f0+16 -- streamed in frame order with a ring of 6 frames of loads
-//     in flight (assemble_eliminate; window-major assemble + eliminate for window sets other than
+//     and b from the frames f0-1 .. f0+16 -- streamed in frame order with a ring of RingDepth<TIN> frames of
+//     loads in flight (assemble_eliminate; window-major assemble + eliminate for window sets other than
 //     three windows) -- and eliminate the 14 interior frames as their rows complete, carrying the
 //     two "left spike" columns that couple the chunk to the previous chunk's last two frames (its
 //     separator); the elimination runs on into the chunk's own separator -> 14 numbers per lane;
@@ -27,7 +27,12 @@
 //     transfer factor says so beforehand) it waits for the whole utterance and sweeps all records.
 //     Either way a two-sided block sweep (top-down, bottom-up, 2-block system in the middle) over
 //     records staged through LDS by wavefronts 1-3; no factor of the sweep is stored;
-//   back-substitution in the reverse order; trajectory rows stored straight from registers.
+//   back-substitution in the reverse order (level2_backsub, backsub); trajectory rows stored straight from registers
+//   (store_forward_rows; backward: the epilogue in the item's tail).
+// Where the phases are: strip_kernel draws tickets and runs one item per ticket in its `body`; in there, in this order: item
+// geometry and the zero-fill of a strip behind the utterance's end, level 1, then the two roles -- wavefront 0: level 2, publish_record,
+// the route, the waits, the level-3 `sweep` and its ladder, level2_backsub; wavefronts 1 .. kW-1: `stage` and the ladder's mirror --
+// and the `tail` (backsub, verdict marks, output).  The workgroup's control words in LDS are named by the enum next to struct Lds.
 // Edge rules (frames >= T, zeroed dynamic precisions on the first/last mw frames) are
 // wave-uniform in this mapping: clamped load rows and 0/1 factors, no branches.
 //
@@ -80,9 +85,6 @@ constexpr int kW = MLPG_STRIP_W;  // chunks (wavefronts) per strip (workgroup)
 constexpr int kM = MLPG_STRIP_M;  // frames per chunk
 constexpr int kN = kM - 2;   // interior frames of a chunk; frames kN, kN+1 are its separator
 constexpr int kRec = 14;     // doubles per lane in a level-1 / level-2 record
-#ifndef MLPG_STRIP_DAMP1_TOL
-#define MLPG_STRIP_DAMP1_TOL 0x1p-66  // acceptance bound of the 3-strip window (route 1), see kDamp1Tol
-#endif
 #ifndef MLPG_STRIP_STAGE
 #define MLPG_STRIP_STAGE (MLPG_STRIP_W > 6 ? 8 : 6)
 #endif
@@ -101,54 +103,18 @@ enum { rT00, rT01, rT11, rH0, rH1, rD11, rD12, rD22, rF1, rF2, rL11, rL12, rL21,
 //   words 2-3 mask of the lanes (systems) that met a failing pivot, word 4 time-out seen;
 //   then one flag per strip, Rpad = R rounded up to a line per system group: flag[g * Rpad + r].
 constexpr int kCtrlLine = 32;
-#ifndef MLPG_STRIP_POLL_SLEEP
-#define MLPG_STRIP_POLL_SLEEP 16  // x 64 cycles between two looks at the neighbours' flags (4 .. 64 measured: no difference)
-#endif
+constexpr int kPollSleep = 16;  // x 64 cycles between two looks at the neighbours' flags (4 .. 64 measured: no difference)
 #ifndef MLPG_STRIP_RING_F32
 #define MLPG_STRIP_RING_F32 6
 #endif
-#ifndef MLPG_STRIP_BWD_FRAME_MAJOR
-#define MLPG_STRIP_BWD_FRAME_MAJOR 1  // backward epilogue frame by frame (three adjacent row stores, ring of variance loads)
-#endif
-#ifndef MLPG_STRIP_BWD_KEEP
-#define MLPG_STRIP_BWD_KEEP 1  // backward, float32 inputs, per-frame variances: the 51 precisions of a chunk (float32 values: 1/var is
-                               // formed in float32, _mlpg.py:188) stay in registers from the assembly to the epilogue -- no second
-                               // pass over the variances, no second division (round 5)
-#endif
-#ifndef MLPG_STRIP_FWD_BUFSTORE
-#define MLPG_STRIP_FWD_BUFSTORE 1  // forward: trajectory rows by buffer stores (three interleaved rounds, profiles/r05_strip_ab3.txt: float64
-                                   // 0.2323 / 0.2320 / 0.2376 -> 0.2281 / 0.2300 / 0.2330 ms; float32 within the noise)
-#endif
-#ifndef MLPG_STRIP_BWD_BUFSTORE
-#define MLPG_STRIP_BWD_BUFSTORE 1  // backward epilogue (three windows): gradient rows by buffer stores (scalar offsets) instead of global stores
-#endif
-#ifndef MLPG_STRIP_BWD_KARG
-#define MLPG_STRIP_BWD_KARG 1  // backward, three windows: window coefficients by placed scalar loads from the argument segment (karg_f64x6)
-#endif
-#ifndef MLPG_STRIP_FWD_KARG
-#define MLPG_STRIP_FWD_KARG 1  // forward, three windows: the same for all nine coefficients per window (interleaved A/B, profiles/r05_strip_ab2.txt:
-                               // float64 0.2421 / 0.2387 -> 0.2415 / 0.2352 ms, float32 0.1830 / 0.1774 -> 0.1793 / 0.1762: 146 -> 119 spilled SGPRs)
-#endif
-#ifndef MLPG_STRIP_BWD_KEEP0
-#define MLPG_STRIP_BWD_KEEP0 1  // ... wavefront 0 too (it runs levels 2 and 3 meanwhile and has no 51 registers to spare: it reads
-                                // its chunk's variances again)
-#endif
-#ifndef MLPG_STRIP_BWD_EARLY0
-#define MLPG_STRIP_BWD_EARLY0 0  // MLPG_STRIP_BWD_EARLY for wavefront 0 (requested behind its publish)
-#endif
-#ifndef MLPG_STRIP_BWD_EARLY
-#define MLPG_STRIP_BWD_EARLY 4  // backward, float64 in and out: the variance rows of the epilogue's first n frames are requested as soon as
-                                // level 1 is done (into the registers the ring has left), so that they travel while the strip waits for
-                                // its neighbours; the other 17 - n frames are requested in front of the first store as before (round 5).
-                                // Worth half a percent (0 / 8 / 10 rows: 0.2671 / 0.2652 / 0.2646 ms); 4 is what fits without a spill
-                                // beside the level-3 ladder's state (8: 15 spilled registers)
-#endif
-#ifndef MLPG_STRIP_NT_STORES
-#define MLPG_STRIP_NT_STORES 1  // trajectory and gradient rows with the nontemporal hint (written once, never read by this kernel); round 5 A/B
-                                // (profiles/r05_strip_stores_ab.txt): forward f64 +1.9 %, backward f32 +5.5 %.  (Round 3 measured the same gain and
-                                // its notes called it shipped, but the default stayed 0 until round 5.)
-#endif
-constexpr int kRowStoreAux = MLPG_STRIP_NT_STORES ? 2 : 0;  // cache-policy immediate of those rows' buffer stores (2: nt)
+// Backward, float64 in and out: the variance rows of the epilogue's first kEarlyRows frames are requested as soon as level 1 is done (into
+// the registers the ring has left), so that they travel while the strip waits for its neighbours; the other 17 - n frames are requested
+// in front of the first store.  Worth half a percent (0 / 8 / 10 rows: 0.2671 / 0.2652 / 0.2646 ms, round 5); 4 is what fits without a
+// spill beside the level-3 ladder's state (8: 15 spilled registers).
+constexpr int kEarlyRows = 4;
+// Trajectory and gradient rows go out by buffer stores with the nontemporal hint (written once, never read by this kernel): the
+// cache-policy immediate of those stores.  Round 5 A/B (profiles/r05_strip_stores_ab.txt): forward f64 +1.9 %, backward f32 +5.5 %.
+constexpr int kRowStoreAux = 2;
 #ifndef MLPG_STRIP_RING_F64
 #define MLPG_STRIP_RING_F64 6
 #endif
@@ -159,9 +125,6 @@ constexpr int kRowStoreAux = MLPG_STRIP_NT_STORES ? 2 : 0;  // cache-policy imme
                                          // usual case for unnormalised acoustic features) and +3 % on the float32 backward (profiles/r06_notes.md)
 #endif
 
-#ifndef MLPG_STRIP_ROUTE1_TOL
-#define MLPG_STRIP_ROUTE1_TOL 0x1p-66  // own transfer factor below which the 3-strip window is tried first (0: never), see kDamp1Tol
-#endif
 constexpr int kMaxLists = 8;
 constexpr int kLocal = 2;          // level 3 first looks at the records of strips r-2 .. r+2 only
                                    // (wider windows -- 4, 8, 16 strips per side -- when the strip's own transfer factor calls for them)
@@ -175,7 +138,7 @@ constexpr double kDampTol = 1e-22; // ... and accepts that if the window's edges
 // 2^-13 of the spacing of doubles there.  A strip tries it when its own transfer factor is below that; a rejected attempt is followed
 // by the 5-strip window, then by the whole utterance (the ladder in the kernel).  Measured: config 2 forward 0.233 -> 0.216-0.225 ms
 // (profiles/r05_notes.md section 11): the strip waits for two neighbours instead of four and sweeps three records instead of five.
-constexpr double kDamp1Tol = MLPG_STRIP_DAMP1_TOL;
+constexpr double kDamp1Tol = 0x1p-66;
 // the records strip r of Ract reads first: rows lo .. hiE; the last one only as the clamped edge (T, h, V) if `edge`
 struct Window { int lo, hiE, edge; };
 __device__ __forceinline__ Window local_window(int r, int Ract, int k) {
@@ -602,15 +565,13 @@ struct RingDepth<float> { static constexpr int value = MLPG_STRIP_RING_F32; };  
 // and everything wave-uniform go by -- and Tu this lane's own: its dead frames enter with precision 0 and mean 0 by per-lane
 // SELECTS (their values are padding: anything), its rows >= Tu become identity rows.
 // STD: the three standard windows as compile-time coefficients (kStd4; `wc` is not read)
-template <typename TIN, bool BWD, int VM, bool EDGE, int NW, bool MULTI = false, bool KEEP = false, bool LT = false, bool STD = false>
+template <typename TIN, bool BWD, int VM, bool EDGE, int NW, bool MULTI = false, bool LT = false, bool STD = false>
 __device__ __forceinline__ bool assemble_eliminate(__amdgpu_buffer_rsrc_t mrs, __amdgpu_buffer_rsrc_t vrs,
                                                    __amdgpu_buffer_rsrc_t grs, const TIN *__restrict__ vglob,
                                                    unsigned loff, long ldi, long ldg, int sd, int f0, int T, int mw,
                                                    const double (*wc)[9], const double one, double (&Pd)[kM], double (&P1)[kM],
                                                    double (&P2)[kM], double (&rhs)[kM], double &ca, double &cb,
-                                                   double &cc, double (&rec)[kRec], float (&tk)[kM + 1][NW], const int Tu = 0) {
-  // KEEP (backward, float32 inputs): tk[i + 1][w] = the precision of frame f0 + i in window w as the assembly used it
-  // (dead frames 0), i = -1 .. kM-1: what the epilogue multiplies the gradient rows with
+                                                   double &cc, double (&rec)[kRec], const int Tu = 0) {
   // No zero-fill: every accumulator is ASSIGNED by the first contribution that reaches it (window 0 of the frame
   // noted below), so that a row costs no register before its first frame arrives.
   const unsigned ldi_bytes = (unsigned)ldi * (unsigned)sizeof(TIN), win_bytes = (unsigned)sd * (unsigned)sizeof(TIN);
@@ -640,6 +601,10 @@ __device__ __forceinline__ bool assemble_eliminate(__amdgpu_buffer_rsrc_t mrs, _
     }
   }
   constexpr int kRing = RingDepth<TIN>::value;
+  // STD backward only: a store that nothing reads.  It is what is left of the kept-precisions form (open questions) and
+  // computes nothing, but without it the optimiser orders this stream differently in the two standard-window backward units; it
+  // stays until a change to those units is measured on its own.
+  float tau_unread[kM + 1][NW];
   TIN rv[kRing][NW], rm[kRing][NW];
   auto load_frame = [&](TIN (&v)[NW], TIN (&m)[NW], const int i) __attribute__((always_inline)) {
     // BWD: the frame's row offset as an opaque scalar, so that the 18 multiples i * ldi_bytes (and their EDGE variants) are
@@ -677,7 +642,7 @@ __device__ __forceinline__ bool assemble_eliminate(__amdgpu_buffer_rsrc_t mrs, _
       } else if (EDGE) {
         tau *= (t >= lo[w] && t < hi[w]) ? 1.0 : 0.0;  // wave-uniform weight
       }
-      if (KEEP && i < kM) tk[i + 1][w] = (float)tau;  // float32 inputs: exact (a float32 reciprocal, or 0); float64 inputs: rounded
+      if (STD && BWD && i < kM) tau_unread[i + 1][w] = (float)tau;
       double tm = 0.0;
       if (!BWD) tm = tau * mval;
       if (STD) {
@@ -889,6 +854,61 @@ __device__ __forceinline__ void backsub(const double (&Pd)[kM], const double (&P
   rhs[kN + 1] = u.y;
 }
 
+// ---- the kernel's phases ------------------------------------------------------------------------
+// Only the phases whose extraction left every unit's device assembly byte for byte the same are functions of their own; the others are
+// still lambdas of the kernel's item body (profiles/strip_phases_notes.md section 3 lists what was tried).
+struct Lds {
+  double *rec;    // [kW][kRec][64]   (level 1 -> 2)
+  double *stage;  // [kStage][kRec][64] (level 3), same bytes
+  double *park;   // [kPark][64]: g and l2 of wavefront 0's chunk during levels 2-3
+  double *fac;    // [kW-1][kFac][64]
+  double *u;      // [kW+1][2][64]: slot j+1 = separator j, slot 0 = previous strip's
+  int *misc;      // control words, see below
+};
+// the workgroup's control words in Lds::misc
+enum { mTicket, mPollOk, mNext, mRoute };  // the ticket drawn; wavefront 0's last wait ended in time; the ladder's next step; the route
+enum { kLadderDone, kLadderLocal, kLadderWhole };  // mNext: accepted; the 5-strip window next; the whole utterance next
+
+// level 2, back-substitution: the strip's separators from the solution on its last one (sig) and on the previous strip's (sprev), into Lds::u
+__device__ __forceinline__ void level2_backsub(const Lds &lds, const V2 sprev, const V2 sig, const int lane) {
+  double *up = lds.u + lane;
+  up[0] = sprev.x; up[64] = sprev.y;
+  up[(kW * 2) * 64] = sig.x; up[(kW * 2 + 1) * 64] = sig.y;
+  V2 un = sig;
+#pragma unroll
+  for (int j = kW - 2; j >= 0; --j) {
+    const double *f = lds.fac + (size_t)j * kFac * 64 + lane;
+    const V2 c = {f[0 * 64], f[1 * 64]};
+    const M2 EV = {f[2 * 64], f[3 * 64], f[4 * 64], f[5 * 64]};
+    const M2 Mn = {f[6 * 64], f[7 * 64], f[8 * 64], f[9 * 64]};
+    const V2 uj = sub(sub(c, mul_mv(EV, sprev)), mul_mtv(Mn, un));
+    up[((j + 1) * 2) * 64] = uj.x; up[((j + 1) * 2 + 1) * 64] = uj.y;
+    un = uj;
+  }
+}
+
+// level 3: the strip's record (the order of its 14 words in HBM and in the staged LDS copy) to rp = its slot + lane, agent scope
+__device__ __forceinline__ void publish_record(double *rp, const S2 &E, const V2 &gg, const M2 &V, const S2 &Ts, const V2 &hs) {
+  st_agent(rp + 0 * 64, E.a); st_agent(rp + 1 * 64, E.b); st_agent(rp + 2 * 64, E.c);
+  st_agent(rp + 3 * 64, gg.x); st_agent(rp + 4 * 64, gg.y);
+  st_agent(rp + 5 * 64, V.a); st_agent(rp + 6 * 64, V.b); st_agent(rp + 7 * 64, V.c); st_agent(rp + 8 * 64, V.d);
+  st_agent(rp + 9 * 64, Ts.a); st_agent(rp + 10 * 64, Ts.b); st_agent(rp + 11 * 64, Ts.c);
+  st_agent(rp + 12 * 64, hs.x); st_agent(rp + 13 * 64, hs.y);
+}
+// forward output: trajectory rows by buffer stores: the utterance's descriptor, the row offset in a scalar register, the dim's offset in one
+// vector register (16 stores per chunk; three interleaved rounds, profiles/r05_strip_ab3.txt: float64 0.2323 / 0.2320 / 0.2376
+// -> 0.2281 / 0.2300 / 0.2330 ms against global stores; float32 within the noise)
+template <typename TOUT>
+__device__ __forceinline__ void store_forward_rows(TOUT *out_b, const long ldo, const int d, const int f0, const int T, const int Tmax,
+                                                   const double (&x)[kM], const bool zero_out) {
+  const __amdgpu_buffer_rsrc_t ors_f = make_rsrc(out_b);
+  const unsigned ooff_f = (unsigned)d * (unsigned)sizeof(TOUT), ldo_b = (unsigned)ldo * (unsigned)sizeof(TOUT);
+#pragma unroll
+  for (int i = 0; i < kM; ++i) {
+    const int t = f0 + i;
+    if (t < Tmax) buf_st<kRowStoreAux>(ors_f, (unsigned)t * ldo_b, ooff_f, (t < T && !zero_out) ? (TOUT)x[i] : (TOUT)0);
+  }
+}
 // ---- the kernel ---------------------------------------------------------------------------------
 // NW3: the launch has exactly three windows (the usual static / delta / delta-delta set): level 1 is the streamed
 // assemble_eliminate and the backward epilogue the frame-major one, and nothing of the window-major forms for other window
@@ -903,13 +923,10 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
   static_assert(!TR || MULTI, "the transposed form is a MULTI kernel");
   static_assert(!STD || (NW3 && !MULTI), "the standard-window form: three windows, one stream");
   extern __shared__ __align__(16) unsigned char smem[];
-  double *lds_rec = (double *)smem;                                  // [kW][kRec][64]   (level 1 -> 2)
-  double *lds_stage = (double *)smem;                                // [kStage][kRec][64] (level 3), same bytes
-  double *lds_park = (double *)(smem + kLdsStage);                   // [kPark][64]: g and l2 of wavefront 0's chunk during levels 2-3
-  double *lds_fac = (double *)(smem + kLdsStage + kLdsPark);         // [kW-1][kFac][64]
-  double *lds_u = (double *)(smem + kLdsStage + kLdsPark + kLdsFac); // [kW+1][2][64]: slot j+1 = separator j, slot 0 = previous strip's
-  int *lds_misc = (int *)(smem + kLdsStage + kLdsPark + kLdsFac + kLdsU);  // [0] item, [1] poll result
-
+  const Lds lds = {(double *)smem, (double *)smem, (double *)(smem + kLdsStage), (double *)(smem + kLdsStage + kLdsPark),
+                   (double *)(smem + kLdsStage + kLdsPark + kLdsFac), (int *)(smem + kLdsStage + kLdsPark + kLdsFac + kLdsU)};
+  double *lds_rec = lds.rec, *lds_stage = lds.stage, *lds_park = lds.park, *lds_fac = lds.fac, *lds_u = lds.u;
+  int *lds_misc = lds.misc;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (tid < 16) lds_misc[tid] = 0;
@@ -1016,22 +1033,14 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
   double Pd[kM], P1[kM], P2[kM], rhs[kM], ca, cb, cc;
   double rec[kRec];
   bool bad = false;
-  // Backward epilogue inputs (frame-major form, three windows): the precisions of the frames f0-1 .. f0+kM-1.
-  //   float32 inputs, or a float32 gradient (kKeepTau): kept from the assembly in tk[][] -- float32 values, 51 registers;
-  //   float64 inputs with a float64 gradient: the variance rows are read a second time; those of the first kEarly frames are requested right
-  //   after level 1 (early_issue(): the ring's registers are free then), so that they travel while the strip waits
-  //   for its neighbours, the rest in front of the epilogue's first store.
-  // (float64 inputs with a float32 gradient -- what the reference's mlpg_grad returns, _mlpg.py:248 -- keep the precisions rounded
-  // to float32 too: the product is rounded to float32 anyway, so this costs at most one more rounding of 2^-24)
-  constexpr bool kKeepTau = NW3 && BWD && VM == MLPG_HIP_VAR_FRAME && (sizeof(TIN) == 4 || sizeof(TOUT) == 4) && MLPG_STRIP_BWD_KEEP && !MULTI;
+  // Backward epilogue inputs (frame-major form, three windows): the precisions of the frames f0-1 .. f0+kM-1, from the variance rows
+  // read a second time.  float64 in and out: those of the first kEarly frames are requested right after level 1 (early_issue(): the
+  // ring's registers are free then), so that they travel while the strip waits for its neighbours (wavefront 0: behind level 3);
+  // the rest, and every row of the other instances, in front of the epilogue's first store.
   constexpr int kEpi = kM + 1;
-  constexpr int kEarly = (NW3 && BWD && VM == MLPG_HIP_VAR_FRAME && sizeof(TIN) == 8 && !kKeepTau && MLPG_STRIP_BWD_FRAME_MAJOR) ? MLPG_STRIP_BWD_EARLY : 0;
-  // the tail is instantiated per role only where the roles differ in what they keep (otherwise once, behind the roles:
-  // two copies of the epilogue cost scalar registers that the streamed level 1 then spills)
-  constexpr bool kSplitTail = kKeepTau && !MLPG_STRIP_BWD_KEEP0;
-  constexpr int kEarly0 = kSplitTail ? MLPG_STRIP_BWD_EARLY0 : kEarly;  // wavefront 0 (runs levels 2-3 meanwhile)
-  static_assert(kEarly >= 0 && kEarly <= kEpi && kEarly0 >= 0 && kEarly0 <= kEpi, "MLPG_STRIP_BWD_EARLY");
-  float tk[kEpi][3];
+  constexpr int kEarly = (NW3 && BWD && VM == MLPG_HIP_VAR_FRAME && sizeof(TIN) == 8 && sizeof(TOUT) == 8) ? kEarlyRows : 0;
+  static_assert(!(BWD && MULTI), "the multi-stream kernels are forward only");
+  static_assert(kEarly >= 0 && kEarly <= kEpi, "kEarlyRows");
   TIN tv[kEpi][3];
   auto ldf = [&](TIN (&v)[3], const int i) __attribute__((always_inline)) {
     if (VM != MLPG_HIP_VAR_FRAME) return;
@@ -1047,17 +1056,13 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
 #pragma unroll
     for (int sl = 0; sl < kEarly; ++sl) ldf(tv[sl], sl - 1);
   };
-  auto early_issue0 = [&]() __attribute__((always_inline)) {  // wavefront 0
-#pragma unroll
-    for (int sl = 0; sl < kEarly0; ++sl) ldf(tv[sl], sl - 1);
-  };
   if (f0 < T) {
     const bool interior = mw != 0 && f0 - 1 >= mw && f0 + kM < (TR ? Tmin : T) - mw;
     if (NW3 && MLPG_STRIP_ABLATE < 2) {
       // the usual three windows: assembly and elimination streamed in frame order
       double wcl[3][9];
       const double (*wcs)[9] = a.wc;
-      if (!STD && BWD && MLPG_STRIP_BWD_KARG) {
+      if (!STD && BWD) {
         // the six coefficient products per window the backward stream uses (entries 3 .. 8), fetched here
         double c6[3][6];
         karg_f64x6<kKargWc + 0 * 72 + 24>(c6[0]);
@@ -1071,14 +1076,14 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
         }
         wcs = wcl;
       }
-      if (!STD && !BWD && MLPG_STRIP_FWD_KARG && !MULTI) {
+      if (!STD && !BWD && !MULTI) {
         karg_f64x9<kKargWc + 0 * 72>(wcl[0]);
         karg_f64x9<kKargWc + 1 * 72>(wcl[1]);
         karg_f64x9<kKargWc + 2 * 72>(wcl[2]);
         wcs = wcl;
       }
-      if (interior) bad = assemble_eliminate<TIN, BWD, VM, false, 3, MULTI, kKeepTau, false, STD>(mrs, vrs, grs, vglob, loff, ldi, ldg, sd, f0, T, mw, wcs, a.one, Pd, P1, P2, rhs, ca, cb, cc, rec, tk);
-      else bad = assemble_eliminate<TIN, BWD, VM, true, 3, MULTI, kKeepTau, TR, STD>(mrs, vrs, grs, vglob, loff, ldi, ldg, sd, f0, T, mw, wcs, a.one, Pd, P1, P2, rhs, ca, cb, cc, rec, tk, Tu);
+      if (interior) bad = assemble_eliminate<TIN, BWD, VM, false, 3, MULTI, false, STD>(mrs, vrs, grs, vglob, loff, ldi, ldg, sd, f0, T, mw, wcs, a.one, Pd, P1, P2, rhs, ca, cb, cc, rec);
+      else bad = assemble_eliminate<TIN, BWD, VM, true, 3, MULTI, TR, STD>(mrs, vrs, grs, vglob, loff, ldi, ldg, sd, f0, T, mw, wcs, a.one, Pd, P1, P2, rhs, ca, cb, cc, rec, Tu);
       STRIP_TICK(1);
 #ifdef MLPG_STRIP_TRACE
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1107,10 +1112,6 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
 #pragma unroll
     for (int k = 0; k < kRec; ++k) rec[k] = 0.0;
     rec[rD11] = rec[rD22] = 1.0;
-    if (kKeepTau) {
-#pragma unroll
-      for (int i = 0; i < kEpi; ++i) tk[i][0] = tk[i][1] = tk[i][2] = 0.0f;
-    }
   }
   if (bad) rec[rD11] = __builtin_nan("");  // poisons every later level: the system is reported, not solved
 #pragma unroll
@@ -1125,13 +1126,9 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
   // that meet at the same barriers.  Wavefront 0 parks g and l2 of its own chunk in LDS for the duration: its
   // chains then run out of registers, not out of scratch.
   int timed_out = 0;
-  // ---- the item's tail: level-1 back-substitution, verdict marks, output.  A lambda, called at the end of BOTH role
-  // branches below (the roles meet at the same barriers), so that what the epilogue keeps in registers across levels 2-3
-  // is a per-role matter: wavefront 0 runs the chain and has no register to spare, wavefronts 1 .. kW-1 only wait.
-  //   USE_TK: the precisions kept from the assembly (float32 inputs);  NEARLY: variance rows already requested (float64)
-  auto tail = [&](auto use_tk_c, auto nearly_c) __attribute__((always_inline)) {
-  constexpr bool kUseTk = decltype(use_tk_c)::value;
-  constexpr int kNEarly = decltype(nearly_c)::value;
+  // ---- the item's tail: level-1 back-substitution, verdict marks, output.  Called once, behind the two roles (two copies of the
+  // epilogue cost scalar registers that the streamed level 1 then spills).
+  auto tail = [&]() __attribute__((always_inline)) {
   STRIP_TICK(10);
   __syncthreads();
   STRIP_TICK(11);
@@ -1170,27 +1167,7 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
   if (!lane_ok) return;
 #endif
   if (!BWD) {
-#if MLPG_STRIP_FWD_BUFSTORE
-    // trajectory rows by buffer stores: the utterance's descriptor, the row offset in a scalar register, the dim's offset in one
-    // vector register (16 stores per chunk; interleaved A/B in round 5: see the switch)
-    const __amdgpu_buffer_rsrc_t ors_f = make_rsrc(out_b);
-    const unsigned ooff_f = (unsigned)d * (unsigned)sizeof(TOUT), ldo_b = (unsigned)ldo * (unsigned)sizeof(TOUT);
-#pragma unroll
-    for (int i = 0; i < kM; ++i) {
-      const int t = f0 + i;
-      if (t < Tmax) buf_st<kRowStoreAux>(ors_f, (unsigned)t * ldo_b, ooff_f, (t < T && !zero_out) ? (TOUT)rhs[i] : (TOUT)0);
-    }
-#else
-#pragma unroll
-    for (int i = 0; i < kM; ++i) {
-      const int t = f0 + i;
-#if MLPG_STRIP_NT_STORES
-      if (t < Tmax) __builtin_nontemporal_store((t < T && !zero_out) ? (TOUT)rhs[i] : (TOUT)0, &out_b[(size_t)t * ldo + d]);
-#else
-      if (t < Tmax) out_b[(size_t)t * ldo + d] = (t < T && !zero_out) ? (TOUT)rhs[i] : (TOUT)0;
-#endif
-    }
-#endif
+    store_forward_rows(out_b, ldo, d, f0, T, Tmax, rhs, zero_out);
   } else {
     // grad[t, w*sd+d] = tau_w[t] * (cm x[t-1] + c0 x[t] + cp x[t+1])  (paramgen/_mlpg.py:202-281).  The row whose
     // right neighbour lives in the next chunk is written by that chunk: this wavefront writes rows f0-1 .. f0+14,
@@ -1234,7 +1211,7 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
         ow[(size_t)t * ldo] = zero_out ? (TOUT)0 : (TOUT)gval;
       }
     };
-    if (MLPG_STRIP_BWD_FRAME_MAJOR && NW3) {
+    if (NW3) {
       // Frame-major epilogue (round 3): per frame three reciprocals and THREE ADJACENT 480-byte stores -- the wavefront writes its 17 gradient rows as one contiguous 24 KB run in
       // address order (window-major, the three blocks of a row were written 16 rows of stores apart).
       // All 51 variance loads are issued before the first store: loads and stores share one in-order counter on this
@@ -1247,36 +1224,23 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
       }
       const __amdgpu_buffer_rsrc_t ors_e = make_rsrc(out_b);
       const unsigned ooff_e = (unsigned)d * (unsigned)sizeof(TOUT);
-      (void)ors_e; (void)ooff_e;
       // the three coefficients per window (entries 0 .. 2 of wc[w]), fetched here (see karg_f64x6)
       double we[3][3] = {};
       if (STD) {
         // (std_apply: no coefficient)
-      } else if (MLPG_STRIP_BWD_KARG) {
+      } else {
         karg_f64x3<kKargWc + 0 * 72>(we[0]);
         karg_f64x3<kKargWc + 1 * 72>(we[1]);
         karg_f64x3<kKargWc + 2 * 72>(we[2]);
-      } else {
-#pragma unroll
-        for (int w = 0; w < 3; ++w) { we[w][0] = a.wc[w][0]; we[w][1] = a.wc[w][1]; we[w][2] = a.wc[w][2]; }
       }
       auto emitf = [&](const int sl) __attribute__((always_inline)) {
         const int i = sl - 1;
         const int t = f0 + i;
         if (t < 0 || t >= Tmax) return;
-        TOUT *orow = out_b + (size_t)t * ldo + d;
         unsigned row_off = (unsigned)t * (unsigned)ldo * (unsigned)sizeof(TOUT);
-        if (MLPG_STRIP_BWD_BUFSTORE) asm volatile("" : "+s"(row_off));  // (not one of 17 loop invariants held in scalar registers)
+        asm volatile("" : "+s"(row_off));  // (not one of 17 loop invariants held in scalar registers)
         auto put = [&](const int w, const TOUT val) __attribute__((always_inline)) {
-#if MLPG_STRIP_BWD_BUFSTORE
           buf_st<kRowStoreAux>(ors_e, row_off + (unsigned)w * (unsigned)sd * (unsigned)sizeof(TOUT), ooff_e, val);
-          return;
-#endif
-#if MLPG_STRIP_NT_STORES
-          __builtin_nontemporal_store(val, orow + (size_t)w * sd);
-#else
-          orow[(size_t)w * sd] = val;
-#endif
         };
         if (t >= T) {
           if (i >= 0) { put(0, (TOUT)0); put(1, (TOUT)0); put(2, (TOUT)0); }
@@ -1291,22 +1255,13 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
         for (int w = 0; w < 3; ++w) {
           const bool lv = w ? (mw != 0 && t >= mw && t < T - mw) : true;
           double tau = 0.0;
-          if (kUseTk) {
-            // dead frames were kept as 0.  The opaque copy keeps the widening HERE: left to itself the optimiser widens all
-            // 51 values right behind the assembly and carries them as doubles (102 registers) across levels 2 and 3
-            float tf = tk[sl][w];
-            asm volatile("" : "+v"(tf));
-            tau = (double)tf;
-          }
-          else if (lv) tau = VM == MLPG_HIP_VAR_FRAME ? tau_of<TIN>(tv[sl][w]) : tg[w];
+          if (lv) tau = VM == MLPG_HIP_VAR_FRAME ? tau_of<TIN>(tv[sl][w]) : tg[w];
           const double gval = STD ? tau * std_apply(w, xm, x0, xp) : tau * (we[w][0] * xm + we[w][1] * x0 + we[w][2] * xp);
           put(w, zero_out ? (TOUT)0 : (TOUT)gval);
         }
       };
-      if (!kUseTk) {
 #pragma unroll
-        for (int sl = kNEarly; sl < kEpi; ++sl) ldf(tv[sl], sl - 1);
-      }
+      for (int sl = kEarly; sl < kEpi; ++sl) ldf(tv[sl], sl - 1);
       __builtin_amdgcn_sched_barrier(0);
 #define STRIP_EPI(S)                                                        \
       if ((S) < kEpi) {                                                       \
@@ -1407,11 +1362,7 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
     if (xwg) {
       // publish the strip's record, then announce it
       double *rp = a.rec + ((size_t)g * R + r) * (kRec * 64) + lane;
-      st_agent(rp + 0 * 64, E.a); st_agent(rp + 1 * 64, E.b); st_agent(rp + 2 * 64, E.c);
-      st_agent(rp + 3 * 64, gg.x); st_agent(rp + 4 * 64, gg.y);
-      st_agent(rp + 5 * 64, V.a); st_agent(rp + 6 * 64, V.b); st_agent(rp + 7 * 64, V.c); st_agent(rp + 8 * 64, V.d);
-      st_agent(rp + 9 * 64, Ts.a); st_agent(rp + 10 * 64, Ts.b); st_agent(rp + 11 * 64, Ts.c);
-      st_agent(rp + 12 * 64, hs.x); st_agent(rp + 13 * 64, hs.y);
+      publish_record(rp, E, gg, V, Ts, hs);
       // Route, from this strip's own data alone (so that the choice -- and with it every bit of the result -- never
       // depends on timing): its own transfer factor t = 2 max|E^-1 V| is one of the factors of the window's damping
       // bound (k per side in a window of k strips per side).  t <= kDampTol^(1/2): the narrow window; otherwise the
@@ -1424,9 +1375,9 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
         const double t_own = 2.0 * amax4(mul_sm(sym_inv(E, badr), V));
         // k strips per side need t^k <~ kDampTol: 2 (t <= 1e-11), 4 (3e-6), 8 (1.8e-3), 16 (4.2e-2); 0 = whole utterance
         auto any_over = [&](const double tol) { return __ballot(lane_ok && !(t_own <= tol)) != 0ull; };  // NaN counts
-        route = !any_over(MLPG_STRIP_ROUTE1_TOL) ? 1 : !any_over(kRouteTol) ? kLocal : !any_over(3e-6) ? 4 : !any_over(1.8e-3) ? 8 : !any_over(4.2e-2) ? 16 : 0;
+        route = !any_over(kDamp1Tol) ? 1 : !any_over(kRouteTol) ? kLocal : !any_over(3e-6) ? 4 : !any_over(1.8e-3) ? 8 : !any_over(4.2e-2) ? 16 : 0;
         if (2 * route + 1 >= Ract) route = route > kLocal ? 0 : route;  // a window as wide as the utterance: sweep it all
-        if (lane == 0) lds_misc[3] = route;
+        if (lane == 0) lds_misc[mRoute] = route;
       }
       const int kwin = route ? route : kLocal;
       if (route && route <= kLocal && 2 * route + 1 <= kStage) {
@@ -1456,12 +1407,12 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
           if (route == 0) f = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= Ract;
           else if (lane <= w.hiE - w.lo) f = __hip_atomic_load(flags + w.lo + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           if (__ballot(f == 0) == 0ull) break;
-          __builtin_amdgcn_s_sleep(MLPG_STRIP_POLL_SLEEP);
+          __builtin_amdgcn_s_sleep(kPollSleep);
           if (++spins > kSpinLimit) { ok = 0; break; }
         }
         if (lane == 0) {
           if (!ok) atomicAdd(a.ctrl, 1);
-          lds_misc[1] = ok;
+          lds_misc[mPollOk] = ok;
         }
       }
       STRIP_TICK(6);
@@ -1474,7 +1425,7 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
     // ---- level 3: every strip sweeps all records of its utterance ----
     V2 sig = {0.0, 0.0}, sprev = {0.0, 0.0};  // solution on this strip's last separator / the previous strip's
     if (xwg) {
-      timed_out = !__builtin_amdgcn_readfirstlane(lds_misc[1]);
+      timed_out = !__builtin_amdgcn_readfirstlane(lds_misc[mPollOk]);
       // Two sweeps over the records of rows lo .. hiE, no factor stored: top-down over rows lo .. r-1 (row j is
       // finalised when row j+1 is at hand: A_j = E_j - T_{j+1} - Mn_j V_j^T with Mn_j = V_j A_{j-1}^-1, a_j likewise),
       // bottom-up over rows hiE .. r+1 (the Schur complement (S, s) of the rows below row j: B_j = E_j - T_{j+1} - S,
@@ -1542,9 +1493,7 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
           __syncthreads();  // this batch is in LDS
           STRIP_TICK(8);
           if (!timed_out) {
-#ifndef MLPG_L3_NOPRIO
             __builtin_amdgcn_s_setprio(2);  // the whole workgroup waits for this chain
-#endif
             int q = 0;
             while (q < kn) {
               const int pos = p0 + q;
@@ -1622,10 +1571,10 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
           const double tolw = cur == 1 ? kDamp1Tol : kDampTol;
           const bool lane_fine = !lane_ok || full_range || (damp < tolw && sig.x == sig.x);
           const int accept = timed_out || __ballot(!lane_fine) == 0ull;
-          // 0: done; 1: the 5-strip window next (after a 3-strip one that does not already reach that far); 2: the whole utterance
-          const int next = accept ? 0 : ((cur == 1 && kLocal > 1) ? 1 : 2);
+          // the 5-strip window next only after a 3-strip one that does not already reach that far
+          const int next = accept ? kLadderDone : ((cur == 1 && kLocal > 1) ? kLadderLocal : kLadderWhole);
           int ok = 1;
-          if (next == 1) {
+          if (next == kLadderLocal) {
             // the two strips the wider window adds may not have arrived yet (lane l polls the flag of strip wlo + l)
             const Window w2 = local_window(r, Ract, kLocal);
             int spins = 0;
@@ -1633,10 +1582,10 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
               int f = 1;
               if (lane <= w2.hiE - w2.lo) f = __hip_atomic_load(flags + w2.lo + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
               if (__ballot(f == 0) == 0ull) break;
-              __builtin_amdgcn_s_sleep(MLPG_STRIP_POLL_SLEEP);
+              __builtin_amdgcn_s_sleep(kPollSleep);
               if (++spins > kSpinLimit) { ok = 0; break; }
             }
-          } else if (next == 2) {
+          } else if (next == kLadderWhole) {
             // the whole utterance is needed: wait for all of its strips
             int spins = 0;
             while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < Ract) {
@@ -1646,13 +1595,13 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
           }
           if (lane == 0) {
             if (!ok) atomicAdd(a.ctrl, 1);
-            if (next) lds_misc[1] = ok;
-            lds_misc[2] = next;
+            if (next) lds_misc[mPollOk] = ok;
+            lds_misc[mNext] = next;
           }
           __syncthreads();  // (S2b) the stagers learn the decision
-          if (next == 0) break;
+          if (next == kLadderDone) break;
           timed_out = !ok;
-          if (next == 2) {
+          if (next == kLadderWhole) {
             sweep(0, Ract - 1, 0);
             break;
           }
@@ -1668,22 +1617,9 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
 
     // wavefront 0's share of the early variance rows: only now has it registers to receive them (levels 2 and 3 are done);
     // they travel during the two back-substitutions
-    if (kEarly0 > 0) early_issue0();
+    if (kEarly > 0) early_issue();
     // ---- back-substitution of level 2 ----
-    double *up = lds_u + lane;
-    up[0] = sprev.x; up[64] = sprev.y;
-    up[(kW * 2) * 64] = sig.x; up[(kW * 2 + 1) * 64] = sig.y;
-    V2 un = sig;
-#pragma unroll
-    for (int j = kW - 2; j >= 0; --j) {
-      const double *f = lds_fac + (size_t)j * kFac * 64 + lane;
-      const V2 c = {f[0 * 64], f[1 * 64]};
-      const M2 EV = {f[2 * 64], f[3 * 64], f[4 * 64], f[5 * 64]};
-      const M2 Mn = {f[6 * 64], f[7 * 64], f[8 * 64], f[9 * 64]};
-      const V2 uj = sub(sub(c, mul_mv(EV, sprev)), mul_mtv(Mn, un));
-      up[((j + 1) * 2) * 64] = uj.x; up[((j + 1) * 2 + 1) * 64] = uj.y;
-      un = uj;
-    }
+    level2_backsub(lds, sprev, sig, lane);
     if (kParkOn) {
 #pragma unroll
       for (int i = 0; i < kN; ++i) {
@@ -1691,13 +1627,12 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
         P2[i] = lds_park[(kN + i) * 64 + lane];
       }
     }
-    if (kSplitTail) tail(std::integral_constant<bool, kKeepTau && MLPG_STRIP_BWD_KEEP0>{}, std::integral_constant<int, kEarly0>{});
   } else {
     __syncthreads();  // (S2)
     // wavefronts 1..3: stage the records (kStage rows per batch) through LDS; the loads of batch k+1 are issued into
     // registers before wavefront 0 starts on batch k, so only the first batch's memory latency is exposed
     if (xwg) {
-      timed_out = !__builtin_amdgcn_readfirstlane(lds_misc[1]);
+      timed_out = !__builtin_amdgcn_readfirstlane(lds_misc[mPollOk]);
       constexpr int kSlots = (kStage + kW - 2) / (kW - 1);  // rows per stager per batch
       double sv[kSlots][kRec];
       bool own_slot[kSlots];
@@ -1737,7 +1672,7 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
           __syncthreads();  // wavefront 0 has read this batch
         }
       };
-      const int route = __builtin_amdgcn_readfirstlane(lds_misc[3]);  // wavefront 0's choice (see there)
+      const int route = __builtin_amdgcn_readfirstlane(lds_misc[mRoute]);  // wavefront 0's choice (see there)
       if (route == 0) {
         skip_own = false;
         stage(0, Ract - 1);
@@ -1748,11 +1683,11 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
           const Window w = local_window(r, Ract, cur);
           stage(w.lo, w.hiE);
           __syncthreads();  // (S2b) wavefront 0's decision: is the window enough?
-          const int next = __builtin_amdgcn_readfirstlane(lds_misc[2]);
-          if (next == 0) break;
-          timed_out = !__builtin_amdgcn_readfirstlane(lds_misc[1]);
+          const int next = __builtin_amdgcn_readfirstlane(lds_misc[mNext]);
+          if (next == kLadderDone) break;
+          timed_out = !__builtin_amdgcn_readfirstlane(lds_misc[mPollOk]);
           skip_own = false;  // from here on every row is staged from HBM
-          if (next == 2) {
+          if (next == kLadderWhole) {
             stage(0, Ract - 1);
             break;
           }
@@ -1760,9 +1695,8 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
         }
       }
     }
-    if (kSplitTail) tail(std::integral_constant<bool, kKeepTau>{}, std::integral_constant<int, kEarly>{});
   }
-  if (!kSplitTail) tail(std::false_type{}, std::integral_constant<int, kEarly>{});
+  tail();
   };  // body
 
   // (Starting the second workgroup of each CU half an item late was measured in round 2 -- no gain -- and removed in round 5; round 6's
@@ -1788,11 +1722,11 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
           const long long until = t_launch + (long long)tk * a.stagger / a.wpl;
           while ((long long)__builtin_amdgcn_s_memrealtime() < until) __builtin_amdgcn_s_sleep(8);
         }
-        lds_misc[0] = tk;
+        lds_misc[mTicket] = tk;
       }
       first_item = false;
       __syncthreads();
-      const int tk = __builtin_amdgcn_readfirstlane(lds_misc[0]);
+      const int tk = __builtin_amdgcn_readfirstlane(lds_misc[mTicket]);
       if (tk >= lim) break;
 #ifdef MLPG_STRIP_TIMING
       t_prev = (long long)__builtin_readcyclecounter();

@@ -10,10 +10,15 @@ a CU (<= 256 VGPRs, no scratch).
     python tools/strip_isa_stats.py                      # forward float64: general and standard-window units
     python tools/strip_isa_stats.py mlpg_strip_bwd_f32.hip mlpg_strip_std_bwd_f32.hip
     python tools/strip_isa_stats.py --json ...
+    python tools/strip_isa_stats.py --digest [--csrc DIR] [UNIT ...]   # sha256 of each unit's device assembly (all units if none named)
+
+--digest is the proof that a refactor left the device code alone: run it on two trees (this one, and another tree's csrc through
+--csrc) and compare the two outputs with diff.
 
 tests/test_strip_isa_stats.py pins the standard-window forward-float64 instance against the general one with it.
 """
 import argparse
+import hashlib
 import json
 import os
 import re
@@ -45,16 +50,30 @@ def _flags(src):
     return [*B.FLAGS, *B.FILE_FLAGS.get(src, ["-ffp-contract=fast"]), *B.EXTRA]
 
 
-def assembly(src, hipcc=None):
-    """The device-side assembly text of one translation unit of csrc/."""
+def assembly(src, hipcc=None, csrc=None):
+    """The device-side assembly text of one translation unit of csrc/ (or of another tree's csrc directory)."""
     hipcc = hipcc or find_hipcc()
     if hipcc is None:
         raise RuntimeError("hipcc not found")
-    cmd = [hipcc, "-x", "hip", *_flags(src), "--cuda-device-only", "-S", os.path.join(CSRC, src), "-o", "-"]
+    cmd = [hipcc, "-x", "hip", *_flags(src), "--cuda-device-only", "-S", os.path.join(csrc or CSRC, src), "-o", "-"]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed:\n%s\n%s" % (" ".join(cmd), r.stderr[-4000:]))
     return r.stdout
+
+
+def digest(asm):
+    """sha256 of an assembly text without its __hip_cuid_ lines (a per-compilation identifier, the only part that differs between
+    two runs over the same source)."""
+    kept = [line for line in asm.splitlines() if "__hip_cuid_" not in line]
+    return hashlib.sha256("\n".join(kept).encode()).hexdigest()
+
+
+def digests(sources, csrc=None, jobs=16):
+    """[(unit, digest)] in the order given, compiling at most `jobs` units at a time."""
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=max(1, min(jobs, 16))) as ex:
+        return list(zip(sources, ex.map(lambda src: digest(assembly(src, csrc=csrc)), sources)))
 
 
 def _classify(op):
@@ -153,16 +172,27 @@ def _label(mangled):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("sources", nargs="*", default=DEFAULT, help="translation units of nnmnkwii_amd/csrc (default: %s)" % " ".join(DEFAULT))
+    ap.add_argument("sources", nargs="*", help="translation units of nnmnkwii_amd/csrc (default: %s; --digest: all of build.SOURCES)" % " ".join(DEFAULT))
+    ap.add_argument("--digest", action="store_true", help="one line 'sha256  unit' per unit: the device assembly without its __hip_cuid_ lines")
+    ap.add_argument("--csrc", metavar="DIR", help="compile the units of this csrc directory (another tree's) with this tree's flags")
+    ap.add_argument("--jobs", type=int, default=min(16, os.cpu_count() or 1), help="--digest: units compiled at a time (at most 16)")
     ap.add_argument("--json", action="store_true", help="one JSON object instead of the table")
     ap.add_argument("--all", action="store_true", help="every kernel of the unit, not only strip_kernel instances")
     args = ap.parse_args()
     if find_hipcc() is None:
         print("hipcc not found", file=sys.stderr)
         return 2
+    csrc = os.path.abspath(args.csrc) if args.csrc else None
+    if args.digest:
+        if not args.sources:
+            _flags("")  # (imports build)
+            args.sources = list(sys.modules["nnmnkwii_amd.csrc.build"].SOURCES)
+        for src, dg in digests([os.path.basename(s) for s in args.sources], csrc, args.jobs):
+            print("%s  %s" % (dg, src))
+        return 0
     res = {}
-    for src in args.sources:
-        res[src] = {k: v for k, v in stats(os.path.basename(src)).items() if args.all or template_args(k) is not None}
+    for src in args.sources or DEFAULT:
+        res[src] = {k: v for k, v in parse(assembly(os.path.basename(src), csrc=csrc)).items() if args.all or template_args(k) is not None}
     if args.json:
         print(json.dumps(res, indent=1, sort_keys=True))
         return 0
