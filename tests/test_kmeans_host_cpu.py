@@ -1,8 +1,9 @@
 """The text of csrc/kmeans.hip run on the CPU (-m "not gpu"): the file is compiled for the host against tests/gmm_host/common.h --
 workgroups as threads on a barrier -- into a stand-alone program (tests/kmeans_host/main.cpp) under the address and
 undefined-behaviour sanitizers, and the seed step and the Lloyd step are compared with tests/kmeans64.py.  This checks the index
-arithmetic, the row tails, the slice and workspace layout, the LDS layout and every bound of an array; the bounds are those of the
-GPU test (tests/test_kmeans_gpu.py): 1e-10 of the reference's maximum, counts and labels exact."""
+arithmetic, the row tails, the slice and workspace layout, the LDS layout and every bound of an array, at N = 65601 with two
+64-row tiles per slice and trailing slices without rows; the bounds are those of the GPU test (tests/test_kmeans_gpu.py): 1e-10
+of the reference's maximum, counts and labels exact."""
 import os
 import subprocess
 
@@ -36,7 +37,7 @@ def program(tmp_path_factory):
     return d, exe
 
 
-@pytest.mark.parametrize("N,F,K", [(1, 1, 1), (63, 2, 3), (65, 17, 16), (130, 50, 16), (67, 128, 2), (20, 5, 64)])
+@pytest.mark.parametrize("N,F,K", [(1, 1, 1), (63, 2, 3), (65, 17, 16), (130, 50, 16), (67, 128, 2), (20, 5, 64), (65601, 1, 2)])
 def test_kernel_text_on_the_host(program, N, F, K):
     d, exe = program
     C = 1 + (N + F + K) % 8
