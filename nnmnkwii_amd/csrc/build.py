@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["capi.hip", "streams_api.hip", "host_api.hip", "mlpg_generic.hip", "mlpg_wave.hip", "mlpg_wave_fwd_f64.hip", "mlpg_wave_fwd_f32.hip",
            "mlpg_wave_bwd_f64.hip", "mlpg_wave_bwd_f32.hip", "mlpg_wave_fused.hip", "mlpg_strip.hip", "mlpg_strip_fwd_f64.hip",
            "mlpg_strip_fwd_f32.hip", "mlpg_strip_bwd_f64.hip", "mlpg_strip_bwd_f32.hip", "mlpg_strip_std_fwd_f64.hip", "mlpg_strip_std_fwd_f32.hip", "mlpg_strip_std_bwd_f64.hip", "mlpg_strip_std_bwd_f32.hip", "mlpg_strip_multi_f64.hip", "mlpg_strip_multi_f32.hip", "mlpg_const.hip", "mlpg_const_fwd_f64.hip", "mlpg_const_fwd_f32.hip", "mlpg_const_bwd_f64.hip", "mlpg_const_bwd_f32.hip", "mlpg_const_multi_f64.hip", "mlpg_const_multi_f32.hip", "mlpg_chunk.hip", "mlpg_chunk_fwd_f64.hip", "mlpg_chunk_fwd_f32.hip", "mlpg_chunk_bwd_f64.hip", "mlpg_chunk_bwd_f32.hip", "mlpg_fir.hip", "mlpg_vargrad.hip", "mlpg_streams_bwd.hip", "dtw.hip", "dtw_fast.hip", "dtw_costs.hip", "modspec.hip", "modspec_chirp.hip", "modspec_dft.hip", "modspec_api.hip", "gmm_em.hip", "kmeans.hip"]
-HEADERS = ["common.h", "device_prims.h", "assemble.h", "vargrad_element.h", "mlpg_wave_impl.h", "mlpg_strip_impl.h", "mlpg_const_impl.h", "mlpg_chunk_impl.h", "modspec_fft.h", os.path.join("..", "..", "include", "mlpg_hip.h")]
+HEADERS = ["common.h", "device_prims.h", "mlpg_strip_geom.h", "assemble.h", "vargrad_element.h", "mlpg_wave_impl.h", "mlpg_strip_impl.h", "mlpg_const_impl.h", "mlpg_chunk_impl.h", "modspec_fft.h", os.path.join("..", "..", "include", "mlpg_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 # The DTW kernels must round exactly like the CPU oracle (separate multiply and add); the MLPG
 # kernels are free to fuse multiply-adds.

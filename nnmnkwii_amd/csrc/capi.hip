@@ -8,6 +8,7 @@
 #include <utility>
 
 #include "common.h"
+#include "mlpg_strip_geom.h"
 
 namespace mlpg {
 
@@ -270,7 +271,7 @@ int dispatch_solve(hipStream_t st, int in_dtype, int out_dtype, int algo, bool b
       }
       case kRouteStripTr: {
         const int rc = launch_strip_tr(st, in_dtype, p, ws, device);
-        if (rc != kStripMultiNotResident) return rc;
+        if (rc != strip::kNotResident) return rc;
         exclude |= kExcludeTr;  // a launch the grid cannot hold: the other kernels
         continue;
       }

@@ -157,8 +157,7 @@ bool strip_tr_preferred(const Problem &p, const WinSet &w, bool backward, int in
 int launch_strip_tr(hipStream_t s, int dtype, const Problem &p, const WinSet &w, int device);
 int launch_strip(hipStream_t s, int dtype, int out_dtype, bool backward, const Problem &p, const WinSet &w,
                  int device, bool try_tr = true);
-// launch_strip_multi's "nothing was enqueued" result: fewer workgroups can be resident than an utterance has strips
-constexpr int kStripMultiNotResident = -1000;
+// (launch_strip_multi returns strip::kNotResident, mlpg_strip_geom.h, if fewer workgroups can be resident than an utterance has strips)
 // forward pass of several streams (p: the parent arrays, sd/D unused) -- per-frame variances, three windows of extent <= 1
 int launch_strip_multi(hipStream_t s, int dtype, const Problem &p, const WinSet &w, const StreamMap &sm, int device);
 bool unit_mse_supported(int Tmax, const WinSet &w);

@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "mlpg_strip_geom.h"
 
 namespace mlpg {
 
@@ -22,16 +23,8 @@ int launch_strip_tr_f64(hipStream_t st, const Problem &p, const WinSet &ws, void
 int launch_strip_tr_f32(hipStream_t st, const Problem &p, const WinSet &ws, void *scratch, int R, bool zero_ctrl, const StreamMap &sm);
 
 namespace {
-#ifndef MLPG_STRIP_W
-#define MLPG_STRIP_W 4
-#endif
-#ifndef MLPG_STRIP_M
-#define MLPG_STRIP_M 16
-#endif
-constexpr int kStripFrames = MLPG_STRIP_M * MLPG_STRIP_W;   // strip::kW * strip::kM
+constexpr int kStripFrames = strip::kFrames;
 constexpr int kMaxStrips = 256;    // strips of one utterance must be able to be resident together (2 per CU)
-constexpr int kRecBytes = 14 * 64 * 8;
-constexpr int kStripNotResident = kStripMultiNotResident;  // = strip::kNotResident (mlpg_strip_impl.h)
 }  // namespace
 
 bool strip_supported(const Problem &p, const WinSet &ws) {
@@ -98,16 +91,16 @@ bool strip_tr_preferred(const Problem &p, const WinSet &ws, bool backward, int i
 namespace {
 std::mutex g_clean_mu;
 std::map<std::pair<int, hipStream_t>, std::pair<unsigned long long, size_t>> g_clean;  // allocation, zero bytes at its head
-// a launch that enqueued nothing (kStripNotResident) after strip_scratch: nothing is known about the control area
+// a launch that enqueued nothing (strip::kNotResident) after strip_scratch: nothing is known about the control area
 void strip_scratch_forget(hipStream_t st, int device) {
   std::lock_guard<std::mutex> lk(g_clean_mu);
   g_clean[{device, st}].second = 0;
 }
 // scratch (control words + records) of one launch and whether its control area is known to be zero already
 void *strip_scratch(hipStream_t st, int device, size_t nsg, int R, bool *zero_ctrl) {
-  const size_t ctrl = (((1 + 16 + nsg) * 32 + nsg * (size_t)((R + 31) / 32 * 32)) * sizeof(int) + 255) / 256 * 256;  // >= strip::ctrl_bytes
+  const size_t ctrl = strip::ctrl_bytes((int)nsg, R);
   unsigned long long gen = 0;
-  void *sc = scratch(device, st, 3, ctrl + nsg * R * kRecBytes, &gen);
+  void *sc = scratch(device, st, 3, ctrl + nsg * R * strip::kRecBytes, &gen);
   if (!sc) return nullptr;
   // The control words must be zero when the kernel starts.  verdict_kernel leaves them zero again, so a launch on
   // the same scratch whose control area is not larger than the previous one's (everything beyond it held records)
@@ -201,7 +194,7 @@ int launch_strip_tr(hipStream_t st, int dtype, const Problem &p, const WinSet &w
   void *sc = strip_scratch(st, device, nsg, R, &zero_ctrl);
   if (!sc) return MLPG_HIP_ENOMEM;
   const int rc = dtype == MLPG_HIP_F32 ? launch_strip_tr_f32(st, p, ws, sc, R, zero_ctrl, sm) : launch_strip_tr_f64(st, p, ws, sc, R, zero_ctrl, sm);
-  if (rc == kStripNotResident) strip_scratch_forget(st, device);
+  if (rc == strip::kNotResident) strip_scratch_forget(st, device);
   return rc;
 }
 
@@ -211,7 +204,7 @@ int launch_strip(hipStream_t st, int dtype, int out_dtype, bool backward, const 
   // try_tr = false: the caller has just been told that the grid cannot hold that form
   if (try_tr && strip_tr_supported(p, ws, backward, dtype, out_dtype)) {
     const int rc = launch_strip_tr(st, dtype, p, ws, device);
-    if (rc != kStripNotResident) return rc;
+    if (rc != strip::kNotResident) return rc;
   }
   const int R = (p.Tmax + kStripFrames - 1) / kStripFrames;
   const int ndg = (p.sd + 63) / 64;
@@ -227,7 +220,7 @@ int launch_strip(hipStream_t st, int dtype, int out_dtype, bool backward, const 
   else
     rc = dtype == MLPG_HIP_F32 ? launch_strip_bwd_f32(st, out_dtype, p, ws, sc, R, ndg, dgw, zero_ctrl)
                                : launch_strip_bwd_f64(st, out_dtype, p, ws, sc, R, ndg, dgw, zero_ctrl);
-  if (rc == kStripNotResident) {
+  if (rc == strip::kNotResident) {
     strip_scratch_forget(st, device);
     // fewer workgroups can be resident than an utterance has strips (a smaller device, or an occupancy the runtime
     // reports lower than expected): nothing was enqueued; the natural-order kernel has no such requirement
@@ -237,7 +230,7 @@ int launch_strip(hipStream_t st, int dtype, int out_dtype, bool backward, const 
 }
 
 // Several streams of one batch in one launch (mlpg_hip_forward_streams): the lanes run over the static dims of all of
-// them, groups of 64.  Returns kStripNotResident (nothing enqueued) if the grid cannot hold an utterance: the caller
+// them, groups of 64.  Returns strip::kNotResident (nothing enqueued) if the grid cannot hold an utterance: the caller
 // then runs the streams one by one.
 int launch_strip_multi(hipStream_t st, int dtype, const Problem &p, const WinSet &ws, const StreamMap &sm, int device) {
   const int R = (p.Tmax + kStripFrames - 1) / kStripFrames;
@@ -249,7 +242,7 @@ int launch_strip_multi(hipStream_t st, int dtype, const Problem &p, const WinSet
   if (!sc) return MLPG_HIP_ENOMEM;
   const int rc = dtype == MLPG_HIP_F32 ? launch_strip_multi_f32(st, p, ws, sc, R, ndg, dgw, zero_ctrl, sm)
                                        : launch_strip_multi_f64(st, p, ws, sc, R, ndg, dgw, zero_ctrl, sm);
-  if (rc == kStripNotResident) strip_scratch_forget(st, device);
+  if (rc == strip::kNotResident) strip_scratch_forget(st, device);
   return rc;
 }
 

@@ -54,6 +54,7 @@
 #include <mutex>
 #include <vector>
 #include "assemble.h"
+#include "mlpg_strip_geom.h"
 
 #ifndef MLPG_STRIP_ABLATE
 #define MLPG_STRIP_ABLATE 0  // profiling only: 1 no inter-workgroup level, 2 = 1 + no elimination, 3 = 2 + no assembly arithmetic
@@ -72,19 +73,11 @@
 namespace mlpg {
 namespace strip {
 
-#ifndef MLPG_STRIP_W
-#define MLPG_STRIP_W 4   // 8: 128-frame strips, one workgroup of 8 wavefronts per CU (experiment; mlpg_strip.hip must match)
-#endif
-#ifndef MLPG_STRIP_M
-#define MLPG_STRIP_M 16  // 8: the 8-frame-chunk experiment of round 5 (profiles/r05_notes.md); mlpg_strip.hip must match
-#endif
+// (MLPG_STRIP_W, MLPG_STRIP_M and with them kW, kM, kRec, the control-area layout and kNotResident: mlpg_strip_geom.h, shared with the host side)
 #ifndef MLPG_STRIP_WGS
 #define MLPG_STRIP_WGS (MLPG_STRIP_W <= 4 ? 2 : 1)  // workgroups per CU the kernel is compiled for (register budget 512 / (W/4 * WGS))
 #endif
-constexpr int kW = MLPG_STRIP_W;  // chunks (wavefronts) per strip (workgroup)
-constexpr int kM = MLPG_STRIP_M;  // frames per chunk
 constexpr int kN = kM - 2;   // interior frames of a chunk; frames kN, kN+1 are its separator
-constexpr int kRec = 14;     // doubles per lane in a level-1 / level-2 record
 #ifndef MLPG_STRIP_STAGE
 #define MLPG_STRIP_STAGE (MLPG_STRIP_W > 6 ? 8 : 6)
 #endif
@@ -97,12 +90,6 @@ constexpr int kSpinLimit = 1 << 20;
 // record slots
 enum { rT00, rT01, rT11, rH0, rH1, rD11, rD12, rD22, rF1, rF2, rL11, rL12, rL21, rL22 };
 
-// Control words, one per 128-byte line (32 ints) so that the pollers of one utterance, the ticket draws and the
-// arrivals of other utterances never queue on the same L2 line:
-//   line 0: spin time-outs;  lines 1 .. 8: ticket of work list x;  line 9 + g: system group g -- word 0 arrivals,
-//   words 2-3 mask of the lanes (systems) that met a failing pivot, word 4 time-out seen;
-//   then one flag per strip, Rpad = R rounded up to a line per system group: flag[g * Rpad + r].
-constexpr int kCtrlLine = 32;
 constexpr int kPollSleep = 16;  // x 64 cycles between two looks at the neighbours' flags (4 .. 64 measured: no difference)
 #ifndef MLPG_STRIP_RING_F32
 #define MLPG_STRIP_RING_F32 6
@@ -125,7 +112,6 @@ constexpr int kRowStoreAux = 2;
                                          // usual case for unnormalised acoustic features) and +3 % on the float32 backward (profiles/r06_notes.md)
 #endif
 
-constexpr int kMaxLists = 8;
 constexpr int kLocal = 2;          // level 3 first looks at the records of strips r-2 .. r+2 only
                                    // (wider windows -- 4, 8, 16 strips per side -- when the strip's own transfer factor calls for them)
 constexpr double kRouteTol = 1e-11; // a strip whose own transfer factor 2 max|E^-1 V| exceeds this (= kDampTol^(1/2)) does not
@@ -168,10 +154,6 @@ __device__ __forceinline__ int row_of(const Order &o, int pos) {
     return o.nt > o.nb ? o.lo + k : o.hiE - k;
   }
   return o.r;
-}
-__host__ __device__ inline int flag_pitch(int R) { return (R + kCtrlLine - 1) / kCtrlLine * kCtrlLine; }
-__host__ __device__ inline size_t ctrl_ints(int nsg, int R) {
-  return (size_t)(1 + kMaxLists + nsg) * kCtrlLine + (size_t)nsg * flag_pitch(R);
 }
 
 struct Args {
@@ -1804,11 +1786,7 @@ __global__ void __launch_bounds__(256) verdict_kernel(const Problem p, const Win
 }
 
 // ---- launcher ------------------------------------------------------------------------------------
-// Scratch layout for one launch: control words, then the records.
-inline size_t ctrl_bytes(int nsg, int R) { return (ctrl_ints(nsg, R) * sizeof(int) + 255) / 256 * 256; }
-
-constexpr int kNotResident = -1000;  // launch_t: the grid cannot hold an utterance's strips; nothing was enqueued
-
+// (scratch layout for one launch -- control words, then the records: ctrl_bytes, mlpg_strip_geom.h)
 // Workgroups of `kern` (threads, dynamic LDS bytes) that are resident at once on the current device: the occupancy
 // the runtime reports x the CU count.  Queried (and the dynamic-LDS attribute set) once per kernel and device.
 inline int resident_grid(const void *kern, int threads, size_t lds, int *out) {

@@ -9,6 +9,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "mlpg_strip_geom.h"
 
 extern "C" const char *mlpg_hip_last_error(void);
 
@@ -334,7 +335,7 @@ int enqueue_merged(const StreamCall &c, const StreamPlan &pl, int algo, const vo
   const WinSet &ws = wsets[pl.ws_of];
   const int rc = pl.merge_strip ? launch_strip_multi(st, c.dtype, pl.p_merged, ws, pl.smap, device)
                                 : launch_const_multi(st, c.dtype, pl.p_merged, ws, pl.smap, device);
-  if (rc != kStripMultiNotResident) return rc;
+  if (rc != strip::kNotResident) return rc;
   for (int k = 0; k < c.n; ++k)
     if (pl.member[k])
       if (int rc2 = enqueue_run(c, stream_run(c, k, algo, mean, out, wsets), wsets, st, device)) return rc2;
