@@ -17,6 +17,10 @@ def _default_dist(x, y):
     return norm(x - y)
 
 
+# Widest frames the MLPG_HIP_DIST_SCALED_*_NP kinds take: numpy sums up to 128 contiguous float64 elements as eight partial sums
+# and splits longer vectors recursively, which the kernel does not follow (launch_fastdtw refuses them, csrc/dtw_fast.hip)
+_NP_MAX_DIMS = 128
+
 _warned = set()
 
 
@@ -41,6 +45,8 @@ def _resolve_dist(dist):
     * anything else: ``None`` -- the caller then evaluates the local costs on the host with the callable itself, one
       call per window cell as upstream fastdtw does, and runs the DP, the back-trace and the window expansion on the GPU
       (``_hip.fastdtw_callable``).
+    The three ``_NP`` kinds follow numpy's summation order for frames of at most 128 dims only; on wider features
+    ``DTWAligner._paths`` takes the host-evaluated route for them as well (the default Euclidean kind has no width limit).
     A recognised callable is only probed on a few random frame pairs, never called per DP cell.
     """
     from .. import metrics
@@ -87,7 +93,11 @@ class DTWAligner(object):
     whole alignment runs on the GPU; ANY other callable is evaluated on the
     host, once per window cell as upstream fastdtw does, and only the DP,
     back-trace and window expansion run on the GPU (reference speed: the
-    interpreter call per cell is the cost, as it is in the reference).
+    interpreter call per cell is the cost, as it is in the reference).  A
+    recognised non-default ``dist`` on features wider than 128 dims takes that
+    host-evaluated route too, with one ``RuntimeWarning``: the kernel follows
+    numpy's summation order of those distances up to 128 elements only.  The
+    default distance runs on the GPU at any width.
 
     ``tie_rule`` (an extension, keyword only): which of equal DP candidates
     wins -- ``"first"`` (upstream's pure-Python recurrence: first minimum of
@@ -136,6 +146,16 @@ class DTWAligner(object):
                 print("DTWAligner: host-evaluated local costs (dist = %r)" % (self.dist,))
             return self._paths_callable(X, Y, tie, dev)
         dist_kind, dist_scale = resolved
+        if dist_kind != _hip.DIST_L2 and X.shape[2] > _NP_MAX_DIMS:
+            # before the route split: device tensors, the host-pointer entry and `devices` all end in the same kernel
+            _warn_once("wide", "DTWAligner: the kernel reproduces numpy's summation order of this `dist` for at most %d feature "
+                               "dims (got %d): the local costs are evaluated on the host, one Python call per window cell, as "
+                               "upstream fastdtw does" % (_NP_MAX_DIMS, X.shape[2]))
+            if getattr(self, "devices", None) is not None:
+                _warn_once("devices", "DTWAligner: `devices` is ignored for a host-evaluated `dist` (the DP runs on the current GPU)")
+            if self.verbose > 0:
+                print("DTWAligner: host-evaluated local costs (dist = %r, %d dims)" % (self.dist, X.shape[2]))
+            return self._paths_callable(X, Y, tie, dev)
         devices = getattr(self, "devices", None)
         if devices is not None or X.nbytes + Y.nbytes >= self._HOST_ENTRY_BYTES or X.shape[0] <= self._HOST_ENTRY_PAIRS:
             out = _hip.fastdtw_host(X, Y, self.radius, dist_kind, dist_scale, tie_rule=tie,
@@ -238,7 +258,8 @@ class IterativeDTWAligner(object):
     :class:`nnmnkwii_amd.baseline.gmm.MLPG` with a static-only window.  Reference behaviours
     kept on purpose: the aligned buffers persist across iterations and only their prefixes are
     rewritten (alignment.py:163-164), the GMM is fitted on the zero padding as well (:175-178), and
-    ``random_state`` is left to numpy's global generator (:170-174).
+    ``random_state`` is left to numpy's global generator (:170-174).  ``dist`` is handled as by
+    :class:`DTWAligner` (its ``_paths``), the host-evaluated route for a recognised ``dist`` above 128 dims included.
 
     Attributes:
         n_iter, dist, radius, verbose, max_iter_gmm, n_components_gmm: as in the reference.

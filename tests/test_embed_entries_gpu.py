@@ -21,6 +21,7 @@ from oracle import dtw as OD
 from oracle import mlpg as O
 from oracle import modspec as OM
 from oracle.mlpg import pack_windows
+from test_dtw_costs_cpu import L1 as NP_L1, L2 as NP_L2, SQL2 as NP_SQL2, NP_DISTS, NP_SCALES
 
 pytestmark = pytest.mark.gpu
 
@@ -161,7 +162,9 @@ def _tracks(rng, t, D):
     return np.cumsum(rng.randn(t, D), 0) * 0.1
 
 
-def _dtw_cell(pairs, radius, tie, check):
+def _dtw_cell(pairs, radius, tie, check, kind=0, scale=1.0, dist=None):
+    """kind / scale: MLPG_HIP_DIST_* and its factor.  dist: the numpy callable of an _NP kind -- the reference is then the literal
+    restatement of fastdtw driven by it (a Python call per window cell: small pairs only), else the C oracle."""
     L, dev, stream = _call()
     N, D = len(pairs), pairs[0][0].shape[1]
     Tx, Ty = max(len(x) for x, _ in pairs), max(len(y) for _, y in pairs)
@@ -173,7 +176,7 @@ def _dtw_cell(pairs, radius, tie, check):
 
     def call(ins, outs, works):
         return L.mlpg_hip_fastdtw(dev, stream, ins["X"].ptr(), ins["Y"].ptr(), ins["lenx"].ptr(), ins["leny"].ptr(), N, Tx, Ty, D,
-                                  radius, 0, 1.0, tie, outs["path_i"].ptr(), outs["path_j"].ptr(), outs["path_len"].ptr(),
+                                  radius, kind, scale, tie, outs["path_i"].ptr(), outs["path_j"].ptr(), outs["path_len"].ptr(),
                                   outs["cost"].ptr())
 
     def same(a, b):
@@ -183,25 +186,41 @@ def _dtw_cell(pairs, radius, tie, check):
             assert np.array_equal(a["path_i"][n, :k], b["path_i"][n, :k]) and np.array_equal(a["path_j"][n, :k], b["path_j"][n, :k]), n
     got = _twice(call, dict(X=X, Y=Y, lenx=lenx, leny=leny),
                  dict(path_i=((N, Tx + Ty), np.int32), path_j=((N, Tx + Ty), np.int32), path_len=((N,), np.int32), cost=((N,), F64)),
-                 same=same, what=("fastdtw", D, radius, tie, N))
+                 same=same, what=("fastdtw", D, radius, tie, N, kind))
     pi, pj, pl, cost = got["path_i"], got["path_j"], got["path_len"], got["cost"]
     assert (pl > 0).all() and (pl <= Tx + Ty).all()
     for n in check:
         x, y = pairs[n]
-        d, path = OD.fastdtw(x, y, radius, tie=tie)
+        if dist is None:
+            d, path = OD.fastdtw(x, y, radius, tie=tie)
+        else:
+            d, path = OD.fastdtw_py(x, y, radius, dist, tie=tie)
+            path = np.asarray(path)
         assert pl[n] == len(path), n
         assert np.array_equal(pi[n, :pl[n]], path[:, 0]) and np.array_equal(pj[n, :pl[n]], path[:, 1]), n
         assert abs(cost[n] - d) <= 1e-12 * max(d, 1e-300), n
 
 
+# D = 13: one full batch of the paired cost, a remainder batch and an odd last element; D = 60: seven full batches and a remainder
 @pytest.mark.parametrize("tie", [0, 1])
 @pytest.mark.parametrize("radius", [1, 2])
-@pytest.mark.parametrize("D", [3, 25])
+@pytest.mark.parametrize("D", [3, 13, 25, 60])
 def test_fastdtw(D, radius, tie):
     rng = np.random.RandomState(100 * D + 10 * radius + tie)
     sizes = [(1, 1), (7, 300), (129, 64), (40, 3)]
     pairs = [(_tracks(rng, tx, D), _tracks(rng, ty, D)) for tx, ty in sizes]
     _dtw_cell(pairs, radius, tie, range(len(pairs)))
+
+
+@pytest.mark.parametrize("D", [8, 13])
+@pytest.mark.parametrize("form", [NP_L2, NP_L1, NP_SQL2])
+def test_fastdtw_numpy_order_kinds(form, D):
+    """The MLPG_HIP_DIST_SCALED_*_NP kinds (numpy's summation order: D = 8 is one block of eight without a tail, D = 13 a block and a
+    tail of five) on the same guarded buffers, against the restatement driven by the numpy expression each kind stands for."""
+    rng = np.random.RandomState(1000 * form + D)
+    sizes = [(1, 1), (40, 3), (33, 17), (9, 40)]
+    pairs = [(_tracks(rng, tx, D), _tracks(rng, ty, D)) for tx, ty in sizes]
+    _dtw_cell(pairs, 1, 0, range(len(pairs)), kind=form + 1, scale=NP_SCALES[form], dist=NP_DISTS[form])
 
 
 def test_fastdtw_two_launch_form():
