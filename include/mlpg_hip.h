@@ -682,6 +682,37 @@ int mlpg_hip_kmeans_lloyd_step(int device, void *stream, const double *X,
                                void *workspace, size_t workspace_bytes);
 
 /*
+ * The Merlin post-filter for mel-cepstra (K8, csrc/postfilter.hip; the reference's postfilters/__init__.py:7-62, whose four
+ * SPTK operations -- freqt, c2acr, mc2b, b2mc -- are restated from their published definitions; parity with the pysptk package
+ * itself is unpinned).  Per frame c of D coefficients, with v = weight * c:
+ *   r0 = c2acr0(freqt(c, order, -alpha), fftlen), p0 = the same of v, b = mc2b(v, alpha), b[0] += log(r0 / p0) / 2,
+ *   out = b2mc(b, alpha).
+ * Limits, checked before a device is selected: 1 <= D <= 64, fftlen a power of two in [4, 4096], D - 1 <= order < fftlen,
+ * |alpha| < 1.
+ *
+ * mlpg_hip_postfilter_table: host code, touches no device.  Writes G (fftlen/2 + 1, D) row-major float64 into HOST memory:
+ * Re DFT_fftlen(freqt(c, order, -alpha))[k] = sum_d G[k][d] c[d] (csrc/postfilter_table.h).  The library keeps no copy.
+ *
+ * mlpg_hip_merlin_post_filter: mgc and out (B, Tmax, .) of `dtype` with row strides ld_in, ld_out >= D in elements (the mgc
+ * columns of a wider multi-stream array are filtered where they lie; the utterance stride is Tmax * ld); out == mgc with equal
+ * strides is allowed (a frame is read whole before it is written).  weight (D doubles) and G (the table above, built with the
+ * same D, alpha and fftlen) are DEVICE pointers.  Arithmetic is float64, storage typed.  lengths: device int32 (B) or NULL; a
+ * frame at or past min(max(len_b, 0), Tmax) is never loaded and the first D elements of its out row are written as exactly 0;
+ * columns of out beyond D are never touched.  B == 0 or Tmax == 0 returns 0 and launches nothing.  One launch, a workgroup per
+ * MLPG_HIP_POSTFILTER_FRAME_TILE frames; no atomics: two calls on the same inputs give the same bits.  The exponentials are not
+ * rescaled: an input whose exp(2 L) overflows gives what the formula gives.
+ */
+#define MLPG_HIP_POSTFILTER_FRAME_TILE 64
+int mlpg_hip_postfilter_table(int D, double alpha, int order, int fftlen,
+                              double *G);
+int mlpg_hip_merlin_post_filter(int device, void *stream, int dtype,
+                                const void *mgc, int64_t ld_in,
+                                const int32_t *lengths, int B, int Tmax, int D,
+                                double alpha, const double *weight,
+                                const double *G, int fftlen, void *out,
+                                int64_t ld_out);
+
+/*
  * Gather rows along the warping path into zero-padded outputs.  Replaces
  * alignment.py:52-54,72-73:  out[n, k, :] = src[n, path[n, k], :] for
  * k < path_len[n], zeros after.  src (N, Tsrc, D), out (N, Tout, D), same dtype.

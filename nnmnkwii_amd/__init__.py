@@ -6,6 +6,7 @@ behind the Python signatures of r9y9/nnmnkwii's hot path.
     nnmnkwii_amd.preprocessing  trim_zeros_frames, delta_features, alignment.DTWAligner / IterativeDTWAligner,
                                 modspec / inv_modspec / modspec_smoothing
     nnmnkwii_amd.baseline.gmm   MLPGBase, MLPG (GMM voice-conversion baseline; caller of paramgen.mlpg)
+    nnmnkwii_amd.postfilters    merlin_post_filter, merlin_post_filter_batch (mel-cepstral post-filter behind MLPG)
     nnmnkwii_amd.mixture        fit_gaussian_mixture, predict_proba, predict, score_samples (full-covariance GMM, float64 EM)
 
 Everything numerical runs in hand-written HIP kernels (``csrc/``) behind the

@@ -72,6 +72,8 @@ EXPORTS = (
     "mlpg_hip_kmeans_workspace_bytes",
     "mlpg_hip_kmeans_seed_step",
     "mlpg_hip_kmeans_lloyd_step",
+    "mlpg_hip_postfilter_table",
+    "mlpg_hip_merlin_post_filter",
 )
 
 
@@ -233,6 +235,10 @@ def lib():
         if L.mlpg_hip_abi_version() != ABI_VERSION:
             raise HipExtensionError("nnmnkwii_amd: %s has ABI version %d, this binding needs %d -- rebuild it with "
                                     "`python nnmnkwii_amd/csrc/build.py`" % (SO_PATH, L.mlpg_hip_abi_version(), ABI_VERSION))
+        L.mlpg_hip_postfilter_table.restype = ci
+        L.mlpg_hip_postfilter_table.argtypes = [ci, cd, ci, ci, vp]
+        L.mlpg_hip_merlin_post_filter.restype = ci
+        L.mlpg_hip_merlin_post_filter.argtypes = [ci, vp, ci, vp, ctypes.c_int64, vp, ci, ci, ci, cd, vp, vp, ci, vp, ctypes.c_int64]
         _lib = L
     return _lib
 
@@ -1291,6 +1297,81 @@ def kmeans_stats(stats):
     raw = stats.cpu().numpy()
     fl = raw.view(np.float64)
     return float(fl[0]), float(fl[1]), int(raw[2]), int(raw[3])
+
+
+POSTFILTER_FRAME_TILE = 64      # MLPG_HIP_POSTFILTER_FRAME_TILE: frames per workgroup of mlpg_hip_merlin_post_filter
+POSTFILTER_MAX_DIM, POSTFILTER_MIN_FFT, POSTFILTER_MAX_FFT = 64, 4, 4096
+_PF_TABLES = {}                 # (device index, D, alpha, order, fftlen) -> G on that device; a few entries, oldest out first
+_PF_TABLES_MAX = 8
+
+
+def postfilter_check(D, alpha, order, fftlen):
+    """ValueError for sizes outside the limits of the post-filter entries (the C entries refuse the same)."""
+    if not 1 <= D <= POSTFILTER_MAX_DIM:
+        raise ValueError("merlin_post_filter: the number of coefficients must be in [1, %d] (got %d)" % (POSTFILTER_MAX_DIM, D))
+    if fftlen < POSTFILTER_MIN_FFT or fftlen > POSTFILTER_MAX_FFT or fftlen & (fftlen - 1):
+        raise ValueError("merlin_post_filter: fftlen must be a power of two in [%d, %d] (got %d)"
+                         % (POSTFILTER_MIN_FFT, POSTFILTER_MAX_FFT, fftlen))
+    if not D - 1 <= order < fftlen:
+        raise ValueError("merlin_post_filter: minimum_phase_order must be in [D - 1, fftlen) = [%d, %d) (got %d)" % (D - 1, fftlen, order))
+    if not abs(alpha) < 1.0:
+        raise ValueError("merlin_post_filter: |alpha| must be below 1 (got %r)" % (alpha,))
+
+
+def postfilter_table_host(D, alpha, order, fftlen):
+    """mlpg_hip_postfilter_table: G (fftlen/2 + 1, D) float64 as a numpy array (host code: no GPU needed)."""
+    D, alpha, order, fftlen = int(D), float(alpha), int(order), int(fftlen)
+    postfilter_check(D, alpha, order, fftlen)
+    G = np.empty((fftlen // 2 + 1, D), dtype=np.float64)
+    _check(lib().mlpg_hip_postfilter_table(D, alpha, order, fftlen, _np(G)), "mlpg_hip_postfilter_table")
+    return G
+
+
+def postfilter_table(device, D, alpha, order, fftlen):
+    """The table on `device`, remembered per (device, D, alpha, order, fftlen): building it costs milliseconds on the host."""
+    torch = torch_mod()
+    key = (device.index, int(D), float(alpha), int(order), int(fftlen))
+    with _lock:
+        G = _PF_TABLES.get(key)
+    if G is None:
+        G = torch.from_numpy(postfilter_table_host(*key[1:])).to(device)
+        with _lock:
+            while len(_PF_TABLES) >= _PF_TABLES_MAX:
+                _PF_TABLES.pop(next(iter(_PF_TABLES)))
+            _PF_TABLES[key] = G
+    return G
+
+
+def _pf_row_stride(t, B, T, D):
+    """The row stride ld of a (B, T, D) view of a dense (B, T, ld) array (columns contiguous, utterance stride T * ld)."""
+    s0, s1, s2 = t.stride()
+    ld = s1 if T > 1 else (s0 if B > 1 else D)
+    if B * T and ((D > 1 and s2 != 1) or ld < D or (T > 1 and B > 1 and s0 != T * ld)):
+        raise HipExtensionError("merlin_post_filter: needs a column slice of a dense (B, Tmax, ld) tensor, got strides %s"
+                                % ((s0, s1, s2),))
+    return ld
+
+
+def merlin_post_filter(mgc, alpha, weight, G, fftlen, lengths=None, out=None):
+    """mlpg_hip_merlin_post_filter on CUDA tensors: mgc (B, Tmax, D) float32 / float64 whose last dimension is contiguous and
+    whose first two are those of a dense (B, Tmax, ld) array (a column slice of one is fine), weight (D) float64, G the table
+    (fftlen/2 + 1, D), lengths int32 (B) or None, out like mgc (None: a new dense tensor; mgc itself: in place).  Enqueued on the
+    current stream."""
+    torch = torch_mod()
+    assert mgc.is_cuda and mgc.dim() == 3
+    B, T, D = mgc.shape
+    dev = mgc.device
+    if out is None:
+        out = torch.empty((B, T, D), dtype=mgc.dtype, device=dev)
+    assert out.shape == mgc.shape and out.dtype == mgc.dtype and out.device == dev
+    lds = [_pf_row_stride(t, B, T, D) for t in (mgc, out)]
+    for t, shape in ((weight, (D,)), (G, (fftlen // 2 + 1, D))):
+        assert t.shape == shape and t.dtype == torch.float64 and t.is_contiguous() and t.device == dev
+    _check_lengths(lengths, B, dev)
+    rc = lib().mlpg_hip_merlin_post_filter(dev.index, _stream(dev), _dt(mgc), _p(mgc), lds[0], _p(lengths), B, T, D, float(alpha),
+                                           _p(weight), _p(G), int(fftlen), _p(out), lds[1])
+    _check(rc, "mlpg_hip_merlin_post_filter")
+    return out
 
 
 def raise_on_status(status, sd):

@@ -9,7 +9,8 @@ Two situations:
 
 * the reference package is importable: the hot-path callables are replaced IN PLACE on its modules
   (``nnmnkwii.paramgen.mlpg`` and friends, the autograd functions, the aligners, ``baseline.gmm.MLPG``,
-  ``delta_features`` / ``trim_zeros_frames`` / the modspec functions, ``util.apply_each2d_*``);
+  ``delta_features`` / ``trim_zeros_frames`` / the modspec functions, ``postfilters.merlin_post_filter``,
+  ``util.apply_each2d_*``);
   everything else of the reference (datasets, frontend, IO ...) keeps working as before;
 * it is not: lightweight ``nnmnkwii`` / ``nnmnkwii.<sub>`` module objects are registered in
   ``sys.modules`` that expose exactly the hot-path surface of SURVEY.md 8(b) and 8(f).
@@ -22,6 +23,7 @@ import types
 
 from . import autograd as _autograd
 from . import paramgen as _paramgen
+from . import postfilters as _postfilters
 from . import preprocessing as _preprocessing
 from . import util as _util
 from .baseline import gmm as _gmm
@@ -41,6 +43,7 @@ _SURFACE = {
     "nnmnkwii.preprocessing.modspec": {k: getattr(_modspec, k) for k in (
         "modspec", "modphase", "inv_modspec", "modspec_smoothing")},
     "nnmnkwii.baseline.gmm": {k: getattr(_gmm, k) for k in ("MLPGBase", "MLPG")},
+    "nnmnkwii.postfilters": {"merlin_post_filter": _postfilters.merlin_post_filter},
     "nnmnkwii.util": {"apply_each2d_padded": _util.apply_each2d_padded, "apply_each2d_trim": _util.apply_each2d_trim,
                       "trim_zeros_frames": _preprocessing.trim_zeros_frames,
                       "delta_features": _preprocessing.delta_features,

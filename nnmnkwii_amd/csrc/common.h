@@ -137,8 +137,9 @@ SideStreams *side_streams(int device);
 // _batch_backward; 18: their direct transform; 19: the fused loss kernel of mlpg_hip_modspec_loss_step; 20: calls of the float64 modulation-spectrum entries that
 // the chirp-z kernel of modspec_chirp.hip served; 21 counts nothing and reads -1; 22, 23, 24: calls of mlpg_hip_gmm_estep, _mstep and
 // _precisions that launched their kernels (gmm_em.hip); 25 counts nothing and reads -1; 26, 27: calls of mlpg_hip_kmeans_seed_step and
-// _lloyd_step that launched their kernels (kmeans.hip))
-enum { kCountGeneric = 0, kCountWave, kCountStrip, kCountStripMulti, kCountConst, kCountFused, kCountChunk, kCountFir, kCountConstMulti, kCountStripTr, kCountHostSmall, kCountHostSmallDirect, kCountUnused12, kCountVarGrad, kCountUnused14, kCountStreamsBwd, kCountUnused16, kCountModspecBatch, kCountModspecBatchDft, kCountModspecLoss, kCountModspecChirp, kCountUnused21, kCountGmmEstep, kCountGmmMstep, kCountGmmPrecisions, kCountUnused25, kCountKmeansSeed, kCountKmeansLloyd, kCountKinds };
+// _lloyd_step that launched their kernels (kmeans.hip); 28 counts nothing and reads -1; 29: calls of mlpg_hip_merlin_post_filter that
+// launched (postfilter.hip))
+enum { kCountGeneric = 0, kCountWave, kCountStrip, kCountStripMulti, kCountConst, kCountFused, kCountChunk, kCountFir, kCountConstMulti, kCountStripTr, kCountHostSmall, kCountHostSmallDirect, kCountUnused12, kCountVarGrad, kCountUnused14, kCountStreamsBwd, kCountUnused16, kCountModspecBatch, kCountModspecBatchDft, kCountModspecLoss, kCountModspecChirp, kCountUnused21, kCountGmmEstep, kCountGmmMstep, kCountGmmPrecisions, kCountUnused25, kCountKmeansSeed, kCountKmeansLloyd, kCountUnused28, kCountPostfilter, kCountKinds };
 void note_launch(int kind);
 // Grow-only scratch, cached per (device, stream, slot): slot 0 generic factor, 1 fastdtw pyramids,
 // 2 generic status, 3 strip records, 4 constant-coefficient kernel (factor table), 5 fastdtw from host costs (D rows, back-pointers), 6 chunked kernel (records, block factors, separator solutions, marks).  Returns nullptr (and sets the error) on failure.
@@ -250,6 +251,9 @@ int launch_dtw_costs(hipStream_t s, int device, int N, int tie_rule, const int32
                      int32_t *path_len, int path_stride, double *cost_out);
 int launch_gmm_convert(hipStream_t s, const double *x, const double *post, const int32_t *mix, const double *mu_x,
                        const double *mu_y, const double *A, long N, int D, int Dy, int M, double *out);
+// postfilter.hip: the Merlin post-filter over the frames of a padded batch, one launch (kind kCountPostfilter)
+int launch_postfilter(hipStream_t s, int dtype, const void *mgc, long ld_in, const int32_t *lengths, int B, int Tmax, int D,
+                      double alpha, const double *weight, const double *G, int fftlen, void *out, long ld_out);
 int launch_gather(hipStream_t s, int dtype, const void *src, const int32_t *path, const int32_t *path_len, int N,
                   int Tsrc, int path_stride, int D, int Tout, void *out);
 

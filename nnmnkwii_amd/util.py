@@ -3,18 +3,22 @@
 Mirrors ``apply_each2d_trim`` / ``apply_each2d_padded`` of /root/reference/nnmnkwii/util/__init__.py:19-66:
 apply a ``(T, D) -> (T', D')`` function to every utterance of a zero-padded ``(N, Tmax, D)`` array and
 collect the results in a zero-padded ``(N, Tmax, D')`` float64 array.  When the function is one of this
-package's batched operations (``paramgen.mlpg``, ``preprocessing.delta_features``) the whole batch goes
+package's batched operations (``paramgen.mlpg``, ``preprocessing.delta_features``,
+``postfilters.merlin_post_filter``) the whole batch goes
 to the GPU in one call instead of N; any other callable is applied per utterance, as in the reference.
 """
 import numpy as np
 
 from . import _hip
+from . import postfilters as _pf
 from .paramgen import _mlpg as _pg
 from .preprocessing import generic as _gen
 
 
 def _batched(func2d, X, lengths, args, kwargs):
     """One-launch equivalents of the per-utterance loop, or None if func2d is not one of ours."""
+    if func2d is _pf.merlin_post_filter and len(args) <= 5:      # (alpha, minimum_phase_order, fftlen, coef, weight)
+        return _pf.merlin_post_filter_batch(X, *args, lengths=lengths, **kwargs)
     if kwargs:
         return None
     if func2d is _pg.mlpg and len(args) == 2:

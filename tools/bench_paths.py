@@ -27,6 +27,10 @@
         on the host against mixture.fit_gaussian_mixture(init="kmeans", max_iter=0): wall time of both, Lloyd iterations of both,
         milliseconds per seed step and per Lloyd step; also written to profiles/kmeans.json (NNMNKWII_KMEANS_PROFILE names
         another file)
+  postfilter : (only with --only postfilter) the Merlin post-filter over a padded 512 x 2000 x 60 mgc batch at the defaults (order
+        511, fftlen 1024), lengths in [1200, 2000], float64 and float32: milliseconds per call, the achieved fraction of the float64
+        matrix peak (flops = valid frames * 2 * 513 * 60 * 2), the numpy model's time per frame on the host as context; also
+        written to profiles/postfilter.json (NNMNKWII_POSTFILTER_PROFILE names another file)
 
 Each line carries the GPU time (HIP events on the launch stream), the algorithmic bytes, GB/s, and a
 bounded CPU baseline from the oracle on the same host (the checker, timed like bench.py's cpu_baseline).
@@ -94,6 +98,7 @@ def wall_time(fn, steps=1000, warmup=50, repeats=3):
 
 
 HBM_PEAK_GBS = 8000.0
+F64_MATRIX_PEAK_TFLOPS = 78.6     # AMD's published float64 matrix rate of the MI355X (v_mfma_f64_16x16x4_f64)
 
 
 _SINK = None      # run(sink=[...]) collects the lines instead of printing them (bench.py's `secondary` object)
@@ -762,6 +767,51 @@ def _run(only, quick, device_index):
         with open(out, "w") as fh:
             json.dump(res, fh, indent=1, sort_keys=True)
             fh.write("\n")
+
+    # ---- postfilter: the Merlin post-filter behind multi-stream MLPG at config-5 scale; only with --only postfilter ----
+    if args.only and "postfilter" in args.only.split(","):
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import postfilter_model as PM
+        from nnmnkwii_amd import postfilters as PF
+        B, T, D, alpha, order, fftlen = (64, 500, 60, 0.58, 511, 1024) if args.quick else (512, 2000, 60, 0.58, 511, 1024)
+        rng = np.random.RandomState(1234)
+        lens = rng.randint(int(0.6 * T), T + 1, size=B).astype(np.int32)
+        frames = int(lens.sum())
+        flops = float(frames) * 2 * (fftlen // 2 + 1) * D * 2
+        lengths = torch.from_numpy(lens).to(dev)
+        t0 = time.perf_counter()
+        G = _hip.postfilter_table_host(D, alpha, order, fftlen)
+        table_ms = (time.perf_counter() - t0) * 1e3
+        res = dict(path="postfilter-config5", B=B, T=T, D=D, alpha=alpha, minimum_phase_order=order, fftlen=fftlen, frames=frames,
+                   flops=flops, f64_matrix_peak_tflops=F64_MATRIX_PEAK_TFLOPS, table_build_host_ms=table_ms,
+                   table_bytes=int(G.nbytes), frame_tile=_hip.POSTFILTER_FRAME_TILE)
+        host = (rng.randn(B, T, D) / (1.0 + np.arange(D)))
+        host[:, :, 0] += rng.uniform(-8.0, 2.0, (B, T))
+        for name, tdt in (("float64", torch.float64), ("float32", torch.float32)):
+            x = torch.from_numpy(host).to(dev).to(tdt)
+            out = torch.empty_like(x)
+            ms = gpu_time(lambda: PF.merlin_post_filter_batch(x, alpha, order, fftlen, lengths=lengths, out=out), steps=20)
+            res["%s_ms" % name] = ms
+            res["%s_tflops" % name] = flops / (ms * 1e9)
+            res["%s_peak_frac" % name] = flops / (ms * 1e9) / F64_MATRIX_PEAK_TFLOPS
+            res["%s_us_per_frame" % name] = ms * 1e3 / frames
+            pick = np.arange(0, min(int(lens[0]), 200), 37)
+            ref = PM.post_filter_literal(x[0, pick].cpu().numpy().astype(np.float64), alpha, order, fftlen)
+            res["%s_rel_err" % name] = float(np.abs(out[0, pick].cpu().numpy() - ref).max() / np.abs(ref).max())
+        nf = 64
+        t0 = time.perf_counter()
+        PM.post_filter_literal(host[0, :nf], alpha, order, fftlen)
+        res["numpy_model_s_per_frame"] = (time.perf_counter() - t0) / nf
+        res["note"] = ("one launch over the padded batch, lengths in [0.6 T, T]; flops = valid frames * 2 products * (fftlen/2 + 1) bins * D "
+                       "* 2 (padding frames and the exponentials not counted); the peak is AMD's published float64 matrix rate for the "
+                       "MI355X; HIP-event medians on settled clocks; the numpy model (%d frames at once, literal recursion) is context, "
+                       "not a baseline: the parent commit has no device path and pysptk is not installed here" % nf)
+        emit(**res)
+        if not args.quick:
+            out_path = os.environ.get("NNMNKWII_POSTFILTER_PROFILE") or os.path.join(ROOT, "profiles", "postfilter.json")
+            with open(out_path, "w") as fh:
+                json.dump(res, fh, indent=1, sort_keys=True)
+                fh.write("\n")
 
     # ---- c3: unit-variance autograd fwd+bwd ----
     if want("c3"):
