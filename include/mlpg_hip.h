@@ -84,8 +84,8 @@ const char *mlpg_hip_last_error(void);
  * variance-gradient kernel of mlpg_hip_backward_var; 15 launches of the stream-table epilogue of mlpg_hip_backward_streams; 17
  * launches of the typed in-LDS FFT kernel of mlpg_hip_modspec_batch / mlpg_hip_modspec_batch_backward, 18 transforms those two
  * calls sent through the direct transform, 19 launches of the fused loss kernel of mlpg_hip_modspec_loss_step; 20 CALLS of
- * mlpg_hip_modspec / _inv_modspec / _modspec_smoothing / _modspec_backward that the chirp-z kernel served (one per call); -1 for
- * any other `kind` (12, 14 and 16 included).
+ * mlpg_hip_modspec / _inv_modspec / _modspec_smoothing / _modspec_backward that the chirp-z kernel served (one per call); 31
+ * launches of the kernel of mlpg_hip_modspec_filter; -1 for any other `kind` (12, 14, 16 and 30 included).
  * (Tests use it to assert WHICH kernel / route a call took.) */
 long long mlpg_hip_launch_count(int kind);
 int mlpg_hip_device_count(void);
@@ -711,6 +711,34 @@ int mlpg_hip_merlin_post_filter(int device, void *stream, int dtype,
                                 double alpha, const double *weight,
                                 const double *G, int fftlen, void *out,
                                 int64_t ld_out);
+
+/*
+ * The modulation-spectrum filter over a padded minibatch (K9, csrc/modspec_filter.hip): the MS post-filter of Takamichi et al.
+ * (ICASSP 2014, TASLP 2016 -- the application the reference's preprocessing/modspec.py cites) and the low-pass smoothing of
+ * modspec_smoothing (:103-167), either or both, in ONE launch (mlpg_hip_launch_count(31)).  The reference has no such call.
+ * With live_b = min(max(lengths[b], 0), Tmax), nb = n/2 + 1, and for every column d < D:
+ *   S = rfft(x[b, :live_b, d], n) (times 1/sqrt(n) if ortho), P = |S|^2;
+ *   k <  limit_bin, tables given: S'_k = S_k * exp(((A[k,d] - 1) log P_k + C[k,d]) / 2), i.e. P'_k = exp(A log P_k + C) with the
+ *                                 phase kept; a bin with P_k == 0 stays 0.  Without tables these bins are unchanged.
+ *   k >= limit_bin:               the rule of mlpg_hip_modspec_smoothing -- log_domain != 0: unit magnitude with the phase kept
+ *                                 (1 for a zero bin), else 0.  limit_bin == nb removes nothing.
+ *   y = irfft(S', n) with the same norm; out[b, t, d] = y[t] for t < live_b and exactly 0 for live_b <= t < Tmax.
+ * x, out: (B, Tmax, .) of `dtype` (float32 / float64 storage, float64 arithmetic) with row strides ld_x, ld_out >= D in elements
+ * (a column slice of a wider matrix; the utterance stride is Tmax * ld); columns beyond D are never touched; a row at or past
+ * live_b is never read.  out == x with equal strides is in place (a workgroup holds its two columns on the chip before it stores
+ * them); any other overlap is the caller's error.  A, C: DEVICE float64 (nb, D) row-major, both or neither (NULL).  lengths:
+ * device int32 (B) or NULL.  Tmax <= n is required.
+ * mlpg_hip_modspec_filter_form(n): 1 for a power of two in [2, 4096] while mlpg_hip_modspec_set_direct's switch is off -- the
+ * lengths the call takes; 0 otherwise (the caller composes mlpg_hip_modspec and mlpg_hip_inv_modspec).
+ * Every argument is checked before a device is selected (MLPG_HIP_EINVAL, the text starts "modspec_filter:").  B == 0 or D == 0
+ * returns 0 and touches nothing; Tmax == 0 writes nothing.  No atomics: two calls on the same inputs give the same bits.
+ */
+int mlpg_hip_modspec_filter_form(int n);
+int mlpg_hip_modspec_filter(int device, void *stream, int dtype, const void *x,
+                            int64_t ld_x, const int32_t *lengths, int B, int Tmax,
+                            int D, int n, int ortho, const double *A,
+                            const double *C, int limit_bin, int log_domain,
+                            void *out, int64_t ld_out);
 
 /*
  * Gather rows along the warping path into zero-padded outputs.  Replaces

@@ -74,6 +74,8 @@ EXPORTS = (
     "mlpg_hip_kmeans_lloyd_step",
     "mlpg_hip_postfilter_table",
     "mlpg_hip_merlin_post_filter",
+    "mlpg_hip_modspec_filter_form",
+    "mlpg_hip_modspec_filter",
 )
 
 
@@ -239,6 +241,10 @@ def lib():
         L.mlpg_hip_postfilter_table.argtypes = [ci, cd, ci, ci, vp]
         L.mlpg_hip_merlin_post_filter.restype = ci
         L.mlpg_hip_merlin_post_filter.argtypes = [ci, vp, ci, vp, ctypes.c_int64, vp, ci, ci, ci, cd, vp, vp, ci, vp, ctypes.c_int64]
+        L.mlpg_hip_modspec_filter_form.restype = ci
+        L.mlpg_hip_modspec_filter_form.argtypes = [ci]
+        L.mlpg_hip_modspec_filter.restype = ci
+        L.mlpg_hip_modspec_filter.argtypes = [ci, vp, ci, vp, ctypes.c_int64, vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp, ctypes.c_int64]
         _lib = L
     return _lib
 
@@ -1342,13 +1348,13 @@ def postfilter_table(device, D, alpha, order, fftlen):
     return G
 
 
-def _pf_row_stride(t, B, T, D):
+def _pf_row_stride(t, B, T, D, who="merlin_post_filter"):
     """The row stride ld of a (B, T, D) view of a dense (B, T, ld) array (columns contiguous, utterance stride T * ld)."""
     s0, s1, s2 = t.stride()
     ld = s1 if T > 1 else (s0 if B > 1 else D)
     if B * T and ((D > 1 and s2 != 1) or ld < D or (T > 1 and B > 1 and s0 != T * ld)):
-        raise HipExtensionError("merlin_post_filter: needs a column slice of a dense (B, Tmax, ld) tensor, got strides %s"
-                                % ((s0, s1, s2),))
+        raise HipExtensionError("%s: needs a column slice of a dense (B, Tmax, ld) tensor, got strides %s"
+                                % (who, (s0, s1, s2)))
     return ld
 
 
@@ -1371,6 +1377,34 @@ def merlin_post_filter(mgc, alpha, weight, G, fftlen, lengths=None, out=None):
     rc = lib().mlpg_hip_merlin_post_filter(dev.index, _stream(dev), _dt(mgc), _p(mgc), lds[0], _p(lengths), B, T, D, float(alpha),
                                            _p(weight), _p(G), int(fftlen), _p(out), lds[1])
     _check(rc, "mlpg_hip_merlin_post_filter")
+    return out
+
+
+def modspec_filter_form(n):
+    """mlpg_hip_modspec_filter_form: 1 when mlpg_hip_modspec_filter takes the DFT length n, 0 when the caller composes the filter."""
+    return int(lib().mlpg_hip_modspec_filter_form(int(n)))
+
+
+def modspec_filter(x, n, A=None, C=None, limit_bin=None, log_domain=True, ortho=False, lengths=None, out=None):
+    """mlpg_hip_modspec_filter on CUDA tensors: x (B, Tmax, D) float32 / float64, a column slice of a dense (B, Tmax, ld) tensor
+    or dense itself; A, C float64 (n/2 + 1, D) or both None; limit_bin in [0, n/2 + 1] (None: n/2 + 1, nothing removed);
+    lengths int32 (B) or None; out like x (None: a new dense tensor; x itself: in place).  Enqueued on the current stream."""
+    torch = torch_mod()
+    assert x.is_cuda and x.dim() == 3
+    B, T, D = x.shape
+    dev = x.device
+    nb = int(n) // 2 + 1
+    if out is None:
+        out = torch.empty((B, T, D), dtype=x.dtype, device=dev)
+    assert out.shape == x.shape and out.dtype == x.dtype and out.device == dev
+    lds = [_pf_row_stride(t, B, T, D, "modspec_filter") for t in (x, out)]
+    for t in (A, C):
+        assert t is None or (t.shape == (nb, D) and t.dtype == torch.float64 and t.is_contiguous() and t.device == dev)
+    _check_lengths(lengths, B, dev)
+    rc = lib().mlpg_hip_modspec_filter(dev.index, _stream(dev), _dt(x), _p(x), lds[0], _p(lengths), B, T, D, int(n), int(bool(ortho)),
+                                       _p(A), _p(C), nb if limit_bin is None else int(limit_bin), int(bool(log_domain)), _p(out),
+                                       lds[1])
+    _check(rc, "mlpg_hip_modspec_filter")
     return out
 
 

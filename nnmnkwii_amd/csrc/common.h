@@ -138,8 +138,8 @@ SideStreams *side_streams(int device);
 // the chirp-z kernel of modspec_chirp.hip served; 21 counts nothing and reads -1; 22, 23, 24: calls of mlpg_hip_gmm_estep, _mstep and
 // _precisions that launched their kernels (gmm_em.hip); 25 counts nothing and reads -1; 26, 27: calls of mlpg_hip_kmeans_seed_step and
 // _lloyd_step that launched their kernels (kmeans.hip); 28 counts nothing and reads -1; 29: calls of mlpg_hip_merlin_post_filter that
-// launched (postfilter.hip))
-enum { kCountGeneric = 0, kCountWave, kCountStrip, kCountStripMulti, kCountConst, kCountFused, kCountChunk, kCountFir, kCountConstMulti, kCountStripTr, kCountHostSmall, kCountHostSmallDirect, kCountUnused12, kCountVarGrad, kCountUnused14, kCountStreamsBwd, kCountUnused16, kCountModspecBatch, kCountModspecBatchDft, kCountModspecLoss, kCountModspecChirp, kCountUnused21, kCountGmmEstep, kCountGmmMstep, kCountGmmPrecisions, kCountUnused25, kCountKmeansSeed, kCountKmeansLloyd, kCountUnused28, kCountPostfilter, kCountKinds };
+// launched (postfilter.hip); 30 counts nothing and reads -1; 31: launches of the kernel of mlpg_hip_modspec_filter (modspec_filter.hip))
+enum { kCountGeneric = 0, kCountWave, kCountStrip, kCountStripMulti, kCountConst, kCountFused, kCountChunk, kCountFir, kCountConstMulti, kCountStripTr, kCountHostSmall, kCountHostSmallDirect, kCountUnused12, kCountVarGrad, kCountUnused14, kCountStreamsBwd, kCountUnused16, kCountModspecBatch, kCountModspecBatchDft, kCountModspecLoss, kCountModspecChirp, kCountUnused21, kCountGmmEstep, kCountGmmMstep, kCountGmmPrecisions, kCountUnused25, kCountKmeansSeed, kCountKmeansLloyd, kCountUnused28, kCountPostfilter, kCountUnused30, kCountModspecFilter, kCountKinds };
 void note_launch(int kind);
 // Grow-only scratch, cached per (device, stream, slot): slot 0 generic factor, 1 fastdtw pyramids,
 // 2 generic status, 3 strip records, 4 constant-coefficient kernel (factor table), 5 fastdtw from host costs (D rows, back-pointers), 6 chunked kernel (records, block factors, separator solutions, marks).  Returns nullptr (and sets the error) on failure.

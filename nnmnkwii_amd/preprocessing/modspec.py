@@ -132,3 +132,101 @@ def modspec_smoothing(x, modfs, n=4096, norm=None, cutoff=50, log_domain=True):
     if not batched:
         out = out[0]
     return np.ascontiguousarray(out.cpu().numpy().astype(rdt, copy=False)) if is_np else out
+
+
+def limit_bin_of(n, modfs, cutoff):
+    """First removed bin of ``modspec_smoothing`` (modspec.py:145-150, :160-163); ``cutoff=None`` removes nothing."""
+    nb = n // 2 + 1
+    if cutoff is None:
+        return nb
+    if modfs is None:
+        raise ValueError("a cutoff frequency needs the modulation sampling frequency modfs")
+    if cutoff > modfs // 2:
+        raise ValueError("Cutoff frequency {} hz must be larger than Nyquist freqeuency {}. hz".format(cutoff, modfs // 2))
+    return min(int(n * cutoff / modfs) + 1, nb)
+
+
+def _composed_filter(x, live, n, ortho, A, C, limit_bin, log_domain):
+    """The filter at a DFT length mlpg_hip_modspec_filter does not take, from the float64 entries: modspec with phase, the table /
+    removal in torch, inv_modspec.  x (B, T, D) CUDA of any float dtype, live (B) int64 CUDA; returns float64 (B, T, D)."""
+    torch = _hip.torch_mod()
+    B, T, D = x.shape
+    rows = torch.arange(T, device=x.device)[None, :, None] < live[:, None, None]
+    xz = torch.where(rows, x.to(torch.float64), torch.zeros((), dtype=torch.float64, device=x.device))   # padding never reaches the transform
+    ms, ph = _hip.modspec(xz, n, ortho, want_phase=True)
+    nb = n // 2 + 1
+    if A is not None:
+        kept = ms[:, :limit_bin]
+        ms[:, :limit_bin] = torch.where(kept > 0, torch.exp(A[:limit_bin] * torch.log(kept) + C[:limit_bin]), kept)
+    if limit_bin < nb:
+        ms[:, limit_bin:] = 1.0 if log_domain else 0.0     # exp(0) / 0
+    y = _hip.inv_modspec(ms, ph, ortho)                    # (B, 2 (nb - 1), D): n, or n - 1 for an odd n as the 2-D function
+    out = torch.zeros((B, T, D), dtype=torch.float64, device=x.device)
+    Ty = min(T, y.shape[1])
+    out[:, :Ty] = torch.where(rows[:, :Ty], y[:, :Ty], out[:, :Ty])
+    return out
+
+
+def filter_batch(who, X, A, C, n, norm, lengths, limit_bin, log_domain, out):
+    """What modspec_smoothing_batch and postfilters.modspec_post_filter_batch share: a padded (B, Tmax, D) batch, numpy or CUDA
+    tensor, float32 / float64, through one launch of mlpg_hip_modspec_filter where it takes n, else composed in float64."""
+    torch = _hip.torch_mod()
+    ortho = _norm_flag(norm)
+    is_tensor = torch.is_tensor(X)
+    if not is_tensor:
+        X = np.asarray(X)
+    if X.ndim != 3:
+        raise ValueError("%s: X must be (B, Tmax, D), got %d dimensions" % (who, X.ndim))
+    B, T, D = (int(s) for s in X.shape)
+    if n < T:                                               # modspec.py:151-154
+        raise RuntimeError("DFT length {} must be larger than time length {}".format(n, T))
+    nb = n // 2 + 1
+    if is_tensor:
+        if not X.is_cuda:
+            if out is not None:
+                raise ValueError("%s: out= is for CUDA tensors" % who)
+            dev = _hip.require_gpu()
+            return filter_batch(who, X.to(dev), A, C, n, norm, lengths, limit_bin, log_domain, None).to(X.device)
+        if X.dtype not in (torch.float32, torch.float64):
+            raise ValueError("%s: float32 or float64 tensors only, got %s" % (who, X.dtype))
+        dev = _hip.require_gpu(X.device)
+        x = X
+    else:
+        if out is not None:
+            raise ValueError("%s: out= is for CUDA tensors" % who)
+        dev = _hip.require_gpu()
+        rdt = X.dtype if X.dtype in (np.float32, np.float64) else np.float64
+        x = torch.from_numpy(np.ascontiguousarray(X, dtype=rdt)).to(dev)
+    if lengths is not None:
+        if not torch.is_tensor(lengths):
+            lengths = torch.from_numpy(np.asarray(lengths).astype(np.int32))
+        lengths = lengths.to(device=dev, dtype=torch.int32).contiguous()
+        if lengths.shape != (B,):
+            raise ValueError("%s: lengths must hold one value per utterance (B = %d)" % (who, B))
+    if A is not None:
+        A, C = (t.to(device=dev, dtype=torch.float64).contiguous() if torch.is_tensor(t)
+                else torch.from_numpy(np.ascontiguousarray(t, dtype=np.float64)).to(dev) for t in (A, C))
+        if A.shape != (nb, D) or C.shape != (nb, D):
+            raise ValueError("%s: the tables must be (n/2 + 1, D) = (%d, %d), got %s and %s"
+                             % (who, nb, D, tuple(A.shape), tuple(C.shape)))
+    if _hip.modspec_filter_form(n):
+        y = _hip.modspec_filter(x, n, A, C, limit_bin, log_domain, ortho, lengths=lengths, out=out if is_tensor else x)
+    else:
+        live = torch.full((B,), T, dtype=torch.int64, device=dev) if lengths is None else lengths.to(torch.int64).clamp(0, T)
+        y = _composed_filter(x, live, n, ortho, A, C, limit_bin, log_domain).to(x.dtype)
+        if out is not None:
+            out.copy_(y)
+            y = out
+    return y if is_tensor else y.cpu().numpy()
+
+
+def modspec_smoothing_batch(X, modfs, n=4096, norm=None, cutoff=50, log_domain=True, lengths=None, out=None):
+    """``modspec_smoothing`` over a padded batch ``(B, Tmax, D)`` in one launch (``mlpg_hip_modspec_filter``).
+
+    ``X``: a numpy array (float32 / float64 keep their dtype; others are computed as float64) or a CUDA tensor (float32 /
+    float64), which may be a slice of the last dimension of a wider dense tensor.  ``lengths``: utterance b's rows at or past
+    ``min(max(lengths[b], 0), Tmax)`` are never read and come out as exact zeros.  ``out`` (tensors only): where the result
+    goes; ``out=X`` smooths in place.  A DFT length that is no power of two, is above 4096 or odd is composed from the float64
+    calls (an odd ``n`` inverts at ``n - 1``, as the 2-D function)."""
+    n = _check_n(n)
+    return filter_batch("modspec_smoothing_batch", X, None, None, n, norm, lengths, limit_bin_of(n, modfs, cutoff), log_domain, out)

@@ -4,21 +4,36 @@ Mirrors ``apply_each2d_trim`` / ``apply_each2d_padded`` of /root/reference/nnmnk
 apply a ``(T, D) -> (T', D')`` function to every utterance of a zero-padded ``(N, Tmax, D)`` array and
 collect the results in a zero-padded ``(N, Tmax, D')`` float64 array.  When the function is one of this
 package's batched operations (``paramgen.mlpg``, ``preprocessing.delta_features``,
-``postfilters.merlin_post_filter``) the whole batch goes
+``postfilters.merlin_post_filter``, ``postfilters.modspec_post_filter``, ``preprocessing.modspec_smoothing``) the whole batch goes
 to the GPU in one call instead of N; any other callable is applied per utterance, as in the reference.
 """
+import inspect
+
 import numpy as np
 
 from . import _hip
 from . import postfilters as _pf
 from .paramgen import _mlpg as _pg
 from .preprocessing import generic as _gen
+from .preprocessing.modspec import modspec_smoothing as _smoothing, modspec_smoothing_batch as _smoothing_batch
 
 
 def _batched(func2d, X, lengths, args, kwargs):
     """One-launch equivalents of the per-utterance loop, or None if func2d is not one of ours."""
     if func2d is _pf.merlin_post_filter and len(args) <= 5:      # (alpha, minimum_phase_order, fftlen, coef, weight)
         return _pf.merlin_post_filter_batch(X, *args, lengths=lengths, **kwargs)
+    if func2d is _smoothing or func2d is _pf.modspec_post_filter:
+        batch = _smoothing_batch if func2d is _smoothing else _pf.modspec_post_filter_batch
+        try:
+            bound = inspect.signature(func2d).bind(None, *args, **kwargs)
+        except TypeError:
+            return None                  # the per-utterance call raises it
+        bound.apply_defaults()
+        kw = dict(bound.arguments)
+        kw.pop("x")
+        if X.shape[1] > int(kw["n"]):
+            return None                  # utterances may still fit; the per-utterance path raises where one does not
+        return batch(X, lengths=lengths, **kw)
     if kwargs:
         return None
     if func2d is _pg.mlpg and len(args) == 2:

@@ -31,6 +31,11 @@
         511, fftlen 1024), lengths in [1200, 2000], float64 and float32: milliseconds per call, the achieved fraction of the float64
         matrix peak (flops = valid frames * 2 * 513 * 60 * 2), the numpy model's time per frame on the host as context; also
         written to profiles/postfilter.json (NNMNKWII_POSTFILTER_PROFILE names another file)
+  msfilter : (only with --only msfilter) the modulation-spectrum post-filter plus low-pass smoothing (tables and cutoff, n = 4096)
+        over the 60 mgc columns of a padded 512 x 2000 x 187 batch, lengths in [1200, 2000], float32 and float64: (a) the one launch
+        of mlpg_hip_modspec_filter on the column slice, (b) the same filter composed from modspec with phase, torch arithmetic and
+        inv_modspec on float64 copies; milliseconds of both, their ratio, the fraction of the HBM floor (x read plus result written
+        at 8 TB/s); also written to profiles/msfilter.json (NNMNKWII_MSFILTER_PROFILE names another file)
 
 Each line carries the GPU time (HIP events on the launch stream), the algorithmic bytes, GB/s, and a
 bounded CPU baseline from the oracle on the same host (the checker, timed like bench.py's cpu_baseline).
@@ -809,6 +814,57 @@ def _run(only, quick, device_index):
         emit(**res)
         if not args.quick:
             out_path = os.environ.get("NNMNKWII_POSTFILTER_PROFILE") or os.path.join(ROOT, "profiles", "postfilter.json")
+            with open(out_path, "w") as fh:
+                json.dump(res, fh, indent=1, sort_keys=True)
+                fh.write("\n")
+
+    # ---- msfilter: the MS post-filter and smoothing on the mgc columns of a config-5 sized batch; only with --only msfilter ----
+    if args.only and "msfilter" in args.only.split(","):
+        from nnmnkwii_amd import postfilters as PF
+        import importlib
+        MS = importlib.import_module("nnmnkwii_amd.preprocessing.modspec")   # (by name: the package re-exports a function `modspec`)
+        B, T, D, ld, n, modfs, cutoff = (32, 500, 60, 187, 4096, 200, 50) if args.quick else (512, 2000, 60, 187, 4096, 200, 50)
+        nb = n // 2 + 1
+        rng = np.random.RandomState(1234)
+        lens = rng.randint(int(0.6 * T), T + 1, size=B).astype(np.int32)
+        lengths = torch.from_numpy(lens).to(dev)
+        live = lengths.to(torch.int64)
+        limit_bin = MS.limit_bin_of(n, modfs, cutoff)
+        A = torch.from_numpy(rng.uniform(0.8, 1.3, (nb, D))).to(dev)
+        C = torch.from_numpy(rng.uniform(-0.5, 0.5, (nb, D))).to(dev)
+        res = dict(path="msfilter-config5", B=B, T=T, D=D, row_stride=ld, n=n, modfs=modfs, cutoff=cutoff, limit_bin=limit_bin,
+                   frames=int(lens.sum()), table_bytes=int(2 * nb * D * 8), hbm_peak_GBps=HBM_PEAK_GBS)
+        for name, tdt, item in (("float32", torch.float32, 4), ("float64", torch.float64, 8)):
+            wide = (0.1 * torch.cumsum(torch.randn(B, T, ld, dtype=torch.float64, device=dev, generator=gen), dim=1)).to(tdt)
+            dst = torch.zeros_like(wide)
+            x, out = wide[..., :D], dst[..., :D]
+            c0 = _hip.lib().mlpg_hip_launch_count(31)
+            ms_a = gpu_time(lambda: PF.modspec_post_filter_batch(x, A, C, n=n, lengths=lengths, modfs=modfs, cutoff=cutoff, out=out),
+                            steps=20)
+            assert _hip.lib().mlpg_hip_launch_count(31) > c0
+            ya = out.to(torch.float64)
+
+            def composed():
+                out.copy_(MS._composed_filter(x, live, n, False, A, C, limit_bin, True))
+
+            ms_b = gpu_time(composed, steps=5, warmup=1, settle_ms=0)
+            yb = out.to(torch.float64)
+            nbytes = 2.0 * B * T * D * item
+            floor_ms = nbytes / (HBM_PEAK_GBS * 1e9) * 1e3
+            res.update({"%s_launch_ms" % name: ms_a, "%s_composed_ms" % name: ms_b, "%s_composed_over_launch" % name: ms_b / ms_a,
+                        "%s_bytes" % name: nbytes, "%s_hbm_floor_ms" % name: floor_ms, "%s_hbm_floor_frac" % name: floor_ms / ms_a,
+                        "%s_us_per_column" % name: ms_a * 1e3 / (B * D),
+                        "%s_launch_vs_composed_rel" % name: float((ya - yb).abs().max() / yb.abs().max())})
+            del wide, dst, x, out, ya, yb
+            torch.cuda.empty_cache()
+        res["note"] = ("(a) one launch of mlpg_hip_modspec_filter on the column slice, in the stored dtype; (b) the same filter from entry "
+                       "points the parent commit has: a masked float64 copy, mlpg_hip_modspec with phase, torch arithmetic on the "
+                       "(B, n/2+1, D) spectra, mlpg_hip_inv_modspec, mask, cast and copy into the slice.  Bytes: x read plus result "
+                       "written over the padded batch; the floor is those bytes at the 8 TB/s HBM peak.  HIP-event medians; (a) on "
+                       "settled clocks over 20 calls, (b) over 5 calls.  Neither time is asserted anywhere")
+        emit(**res)
+        if not args.quick:
+            out_path = os.environ.get("NNMNKWII_MSFILTER_PROFILE") or os.path.join(ROOT, "profiles", "msfilter.json")
             with open(out_path, "w") as fh:
                 json.dump(res, fh, indent=1, sort_keys=True)
                 fh.write("\n")
