@@ -85,7 +85,8 @@ const char *mlpg_hip_last_error(void);
  * launches of the typed in-LDS FFT kernel of mlpg_hip_modspec_batch / mlpg_hip_modspec_batch_backward, 18 transforms those two
  * calls sent through the direct transform, 19 launches of the fused loss kernel of mlpg_hip_modspec_loss_step; 20 CALLS of
  * mlpg_hip_modspec / _inv_modspec / _modspec_smoothing / _modspec_backward that the chirp-z kernel served (one per call); 31
- * launches of the kernel of mlpg_hip_modspec_filter; -1 for any other `kind` (12, 14, 16 and 30 included).
+ * launches of the kernel of mlpg_hip_modspec_filter; 33 launches of the kernel of mlpg_hip_gmm_trajectory_stats; -1 for any other
+ * `kind` (12, 14, 16, 30 and 32 included).
  * (Tests use it to assert WHICH kernel / route a call took.) */
 long long mlpg_hip_launch_count(int kind);
 int mlpg_hip_device_count(void);
@@ -739,6 +740,32 @@ int mlpg_hip_modspec_filter(int device, void *stream, int dtype, const void *x,
                             int D, int n, int ortho, const double *A,
                             const double *C, int limit_bin, int log_domain,
                             void *out, int64_t ld_out);
+
+/*
+ * The statistics of trajectory GMM conversion over a padded batch (K10, csrc/gmm_traj.hip; the reference's
+ * baseline/gmm.py:225-247, MLPG.transform): ONE launch (mlpg_hip_launch_count(33)) turns source frames and their hard mixture
+ * labels into the two inputs of mlpg_hip_forward.  All float64; row (b, t) of x, mean and var is at base + (b * Tmax + t) * ld
+ * with row strides ld_x, ld_mean, ld_var >= D in elements (column slices of wider arrays, such as the source half of a joint
+ * [x | y] matrix); columns D .. ld - 1 of mean and var are never touched.  labels int32 (B * Tmax), mu_x and mu_y (M, D),
+ * A (M, D, D) = covarYX covarXX^-1 row-major, cvar (M, D) = the diagonal approximation of eq. 23 (gmm.py:245); lengths: device
+ * int32 (B) or NULL (every row live).  With live_b = min(max(lengths[b], 0), Tmax):
+ *   t <  live_b, m = labels[b * Tmax + t] in [0, M):   mean = mu_y[m] + A[m] (x - mu_x[m]),  var = cvar[m] (copied bit for bit);
+ *   t <  live_b, m outside [0, M):                     the D elements of the mean row and of the var row are NaN (nothing is read
+ *                                                      out of bounds; x of that row is not read);
+ *   t >= live_b:                                       mean = 0 and var = 1 exactly; neither x nor the label of the row is read.
+ * Limits: 1 <= D <= 128, 1 <= M <= 65536, B, Tmax >= 0.  Every argument is checked before a device is selected; B == 0 or
+ * Tmax == 0 returns 0 and touches nothing.  A workgroup takes MLPG_HIP_GMM_TRAJ_ROW_TILE rows of the flattened (B * Tmax) axis.
+ * No floating-point atomics and one summation order over k: a row's result does not depend on what else is in its tile or batch,
+ * and two calls give the same bits.
+ */
+#define MLPG_HIP_GMM_TRAJ_ROW_TILE 64
+int mlpg_hip_gmm_trajectory_stats(int device, void *stream, const double *x,
+                                  int64_t ld_x, const int32_t *lengths, int B,
+                                  int Tmax, int D, const int32_t *labels,
+                                  const double *mu_x, const double *mu_y,
+                                  const double *A, const double *cvar, int M,
+                                  double *mean, int64_t ld_mean, double *var,
+                                  int64_t ld_var);
 
 /*
  * Gather rows along the warping path into zero-padded outputs.  Replaces

@@ -76,6 +76,7 @@ EXPORTS = (
     "mlpg_hip_merlin_post_filter",
     "mlpg_hip_modspec_filter_form",
     "mlpg_hip_modspec_filter",
+    "mlpg_hip_gmm_trajectory_stats",
 )
 
 
@@ -245,6 +246,9 @@ def lib():
         L.mlpg_hip_modspec_filter_form.argtypes = [ci]
         L.mlpg_hip_modspec_filter.restype = ci
         L.mlpg_hip_modspec_filter.argtypes = [ci, vp, ci, vp, ctypes.c_int64, vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp, ctypes.c_int64]
+        L.mlpg_hip_gmm_trajectory_stats.restype = ci
+        L.mlpg_hip_gmm_trajectory_stats.argtypes = [ci, vp, vp, ctypes.c_int64, vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, ctypes.c_int64,
+                                                    vp, ctypes.c_int64]
         _lib = L
     return _lib
 
@@ -1406,6 +1410,51 @@ def modspec_filter(x, n, A=None, C=None, limit_bin=None, log_domain=True, ortho=
                                        lds[1])
     _check(rc, "mlpg_hip_modspec_filter")
     return out
+
+
+GMM_TRAJ_ROW_TILE = 64          # MLPG_HIP_GMM_TRAJ_ROW_TILE: rows of the (B * Tmax) axis per workgroup of mlpg_hip_gmm_trajectory_stats
+GMM_TRAJ_MAX_MIXTURES = 65536
+
+
+def gmm_trajectory_stats(x, lengths, labels, mu_x, mu_y, A, cvar, mean=None, var=None):
+    """mlpg_hip_gmm_trajectory_stats on float64 CUDA tensors: x (B, Tmax, D) whose last dimension is contiguous and whose first
+    two are those of a dense (B, Tmax, ld) array (a column slice of one is fine), lengths int32 (B) or None, labels int32
+    (B, Tmax) or (B * Tmax), mu_x, mu_y, cvar (M, D), A (M, D, D).  Returns (mean, var), each (B, Tmax, D): mu_y[m] + A[m] (x -
+    mu_x[m]) and cvar[m] for the label m of a live row, 0 and 1 on the rows past an utterance's length.  mean / var: where to
+    write them (column slices allowed; columns outside are not touched), new dense tensors when None.  Enqueued on the current
+    stream."""
+    torch = torch_mod()
+    for name, t in (("x", x), ("mu_x", mu_x), ("mu_y", mu_y), ("A", A), ("cvar", cvar), ("mean", mean), ("var", var)):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float64 or not t.is_cuda):
+            raise ValueError("gmm_trajectory_stats: %s must be a float64 CUDA tensor, got %s"
+                             % (name, "%s on %s" % (t.dtype, t.device) if torch.is_tensor(t) else type(t).__name__))
+    if not torch.is_tensor(labels) or labels.dtype != torch.int32 or not labels.is_cuda:
+        raise ValueError("gmm_trajectory_stats: labels must be an int32 CUDA tensor")
+    if x.dim() != 3:
+        raise ValueError("gmm_trajectory_stats: x must be (B, Tmax, D), got %d dimensions" % x.dim())
+    B, T, D = x.shape
+    M = mu_x.shape[0]
+    if not 1 <= D <= GMM_MAX_FEATURES or not 1 <= M <= GMM_TRAJ_MAX_MIXTURES:
+        raise ValueError("gmm_trajectory_stats: takes 1 to %d features and 1 to %d mixtures, got %d and %d"
+                         % (GMM_MAX_FEATURES, GMM_TRAJ_MAX_MIXTURES, D, M))
+    dev = x.device
+    for t, shape in ((mu_x, (M, D)), (mu_y, (M, D)), (A, (M, D, D)), (cvar, (M, D))):
+        if t.shape != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError("gmm_trajectory_stats: the model tensors must be contiguous (M, D), (M, D), (M, D, D), (M, D) on x's device")
+    if labels.numel() != B * T or not labels.is_contiguous() or labels.device != dev:
+        raise ValueError("gmm_trajectory_stats: labels must hold B * Tmax = %d contiguous entries on x's device" % (B * T))
+    _check_lengths(lengths, B, dev)
+    if mean is None:
+        mean = torch.empty((B, T, D), dtype=torch.float64, device=dev)
+    if var is None:
+        var = torch.empty((B, T, D), dtype=torch.float64, device=dev)
+    if mean.shape != x.shape or var.shape != x.shape or mean.device != dev or var.device != dev:
+        raise ValueError("gmm_trajectory_stats: mean and var must have x's shape and device")
+    lds = [_pf_row_stride(t, B, T, D, "gmm_trajectory_stats") for t in (x, mean, var)]
+    rc = lib().mlpg_hip_gmm_trajectory_stats(dev.index, _stream(dev), _p(x), lds[0], _p(lengths), B, T, D, _p(labels), _p(mu_x),
+                                             _p(mu_y), _p(A), _p(cvar), M, _p(mean), lds[1], _p(var), lds[2])
+    _check(rc, "mlpg_hip_gmm_trajectory_stats")
+    return mean, var
 
 
 def raise_on_status(status, sd):

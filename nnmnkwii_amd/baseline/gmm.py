@@ -8,7 +8,9 @@ mixture, gmm.py:111-113,225-229) is ONE launch of ``mlpg_hip_gmm_convert`` over 
 (the M regression matrices ``S_yx S_xx^-1`` are formed once per model on the host), and the
 trajectory generation -- the expensive part -- goes to the HIP MLPG kernels through
 :func:`nnmnkwii_amd.paramgen.mlpg`.  ``transform_batch`` converts a whole list of utterances
-with one launch (what ``IterativeDTWAligner`` calls every iteration).
+with one launch (what ``IterativeDTWAligner`` calls every iteration).  ``MLPG.transform_padded`` / ``MLPG.transform_batch`` run
+the trajectory conversion of a whole padded batch in three launches -- E-step labels, ``mlpg_hip_gmm_trajectory_stats``, batched
+MLPG -- with the model resident on the device.
 """
 import numpy as np
 from scipy import linalg as _sla
@@ -171,3 +173,82 @@ class MLPG(MLPGBase):
         dg = lambda a: np.diagonal(a, axis1=1, axis2=2)                   # noqa: E731
         Dm = dg(self.covarYY) - dg(self.covarYX) / dg(self.covarXX) * dg(self.covarXY)   # eq. 23, diagonal approx.
         return _mlpg(E, np.ascontiguousarray(Dm[mix]), self.windows)
+
+    def _device_model(self, dev):
+        """(mu_x, mu_y, A, cvar, the E-step model of p(x)) as float64 tensors on ``dev``, uploaded once per device."""
+        cache = self.__dict__.setdefault("_dev_models", {})
+        got = cache.get(dev.index)
+        if got is None:
+            from .. import mixture as _mix
+            torch = _hip.torch_mod()
+            f64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)  # noqa: E731
+            dg = lambda a: np.diagonal(a, axis1=1, axis2=2)               # noqa: E731
+            cvar = dg(self.covarYY) - dg(self.covarYX) / dg(self.covarXX) * dg(self.covarXY)   # eq. 23, as in transform
+            px = _mix._model(self.px, dev) if self.posterior == "device" else None
+            got = cache[dev.index] = (f64(self.src_means), f64(self.tgt_means), f64(self._regression()), f64(cvar), px)
+        return got
+
+    def transform_padded(self, X, lengths=None):
+        """``transform`` over a zero-padded batch: ``X`` (B, Tmax, D) static+delta features, numpy of any float dtype or a
+        float64 CUDA tensor; ``lengths`` (B,) the live frames per utterance (None: all).  Returns (B, Tmax, static_dim) float64
+        of the same kind (what the reference's ``mlpg(E, D, windows)`` returns whatever the dtype of ``src``); frames beyond
+        ``lengths`` are zero.  Three launches -- the labels (``posterior="device"``: one E-step over all rows;
+        ``"sklearn"``: ``px.predict`` on the live rows on the host, uploaded), ``mlpg_hip_gmm_trajectory_stats``, batched MLPG --
+        and with ``posterior="device"`` nothing leaves the device between them."""
+        from ..paramgen import mlpg_batch as _mlpg_batch
+        torch = _hip.torch_mod()
+        is_tensor = torch.is_tensor(X)
+        if not is_tensor:
+            X = np.asarray(X)
+        if (X.dim() if is_tensor else X.ndim) != 3:
+            raise ValueError("transform_padded takes a (B, Tmax, D) batch")
+        B, T, D = X.shape
+        if D == self.static_dim:
+            raise ValueError("transform_padded is the trajectory conversion of static+delta features; static-only input "
+                             "(feature dim == static dim == %d) goes through transform_batch" % D)
+        if D != self.src_means.shape[1]:
+            raise ValueError("X has %d features, the model has %d" % (D, self.src_means.shape[1]))
+        if is_tensor:
+            if not X.is_cuda or X.dtype != torch.float64:
+                raise ValueError("tensor input must be a float64 CUDA tensor, got %s on %s" % (X.dtype, X.device))
+            dev = _hip.require_gpu(X.device)
+            x = X.contiguous()
+        else:
+            dev = _hip.require_gpu()
+            x = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(dev)
+        L = None
+        if lengths is not None:
+            L = (lengths if torch.is_tensor(lengths) else torch.from_numpy(np.asarray(lengths).astype(np.int32))).to(
+                device=dev, dtype=torch.int32).contiguous()
+            if L.shape != (B,):
+                raise ValueError("lengths must have one entry per utterance")
+        if B * T == 0:
+            y = torch.zeros((B, T, self.static_dim), dtype=torch.float64, device=dev)
+            return y if is_tensor else y.cpu().numpy()
+        mu_x, mu_y, A, cvar, px = self._device_model(dev)
+        if self.posterior == "device":
+            labels = _hip.gmm_estep(x.view(B * T, D), *px, want_resp=False, want_labels=True)[2]
+        else:
+            xh = x.cpu().numpy() if is_tensor else np.ascontiguousarray(X, dtype=np.float64)
+            live = np.arange(T)[None, :] < (np.full(B, T) if L is None else np.clip(L.cpu().numpy(), 0, T))[:, None]
+            lab = np.zeros((B, T), dtype=np.int32)
+            if live.any():
+                lab[live] = self.px.predict(xh[live])
+            labels = torch.from_numpy(lab).to(dev)
+        mean, var = _hip.gmm_trajectory_stats(x, L, labels, mu_x, mu_y, A, cvar)
+        y = _mlpg_batch(mean, var, self.windows, L)
+        return y if is_tensor else y.cpu().numpy()
+
+    def transform_batch(self, utterances):
+        """``[transform(x) for x in utterances]``.  Static+delta input: the utterances are packed into one zero-padded batch and
+        converted by ``transform_padded``; the result is a list of (T_i, static_dim) float64 arrays.  Static-only input keeps
+        the frame-wise conversion of ``MLPGBase.transform_batch``."""
+        utterances = [np.asarray(u) for u in utterances]
+        if not utterances or utterances[0].shape[1] == self.static_dim:
+            return super(MLPG, self).transform_batch(utterances)
+        lens = np.array([len(u) for u in utterances], dtype=np.int32)
+        X = np.zeros((len(utterances), int(lens.max()), utterances[0].shape[1]), dtype=np.float64)
+        for i, u in enumerate(utterances):
+            X[i, :len(u)] = u
+        Y = self.transform_padded(X, lens)
+        return [Y[i, :n].copy() for i, n in enumerate(lens)]

@@ -138,8 +138,9 @@ SideStreams *side_streams(int device);
 // the chirp-z kernel of modspec_chirp.hip served; 21 counts nothing and reads -1; 22, 23, 24: calls of mlpg_hip_gmm_estep, _mstep and
 // _precisions that launched their kernels (gmm_em.hip); 25 counts nothing and reads -1; 26, 27: calls of mlpg_hip_kmeans_seed_step and
 // _lloyd_step that launched their kernels (kmeans.hip); 28 counts nothing and reads -1; 29: calls of mlpg_hip_merlin_post_filter that
-// launched (postfilter.hip); 30 counts nothing and reads -1; 31: launches of the kernel of mlpg_hip_modspec_filter (modspec_filter.hip))
-enum { kCountGeneric = 0, kCountWave, kCountStrip, kCountStripMulti, kCountConst, kCountFused, kCountChunk, kCountFir, kCountConstMulti, kCountStripTr, kCountHostSmall, kCountHostSmallDirect, kCountUnused12, kCountVarGrad, kCountUnused14, kCountStreamsBwd, kCountUnused16, kCountModspecBatch, kCountModspecBatchDft, kCountModspecLoss, kCountModspecChirp, kCountUnused21, kCountGmmEstep, kCountGmmMstep, kCountGmmPrecisions, kCountUnused25, kCountKmeansSeed, kCountKmeansLloyd, kCountUnused28, kCountPostfilter, kCountUnused30, kCountModspecFilter, kCountKinds };
+// launched (postfilter.hip); 30 counts nothing and reads -1; 31: launches of the kernel of mlpg_hip_modspec_filter (modspec_filter.hip); 32 counts nothing and reads -1; 33: launches of the
+// kernel of mlpg_hip_gmm_trajectory_stats (gmm_traj.hip))
+enum { kCountGeneric = 0, kCountWave, kCountStrip, kCountStripMulti, kCountConst, kCountFused, kCountChunk, kCountFir, kCountConstMulti, kCountStripTr, kCountHostSmall, kCountHostSmallDirect, kCountUnused12, kCountVarGrad, kCountUnused14, kCountStreamsBwd, kCountUnused16, kCountModspecBatch, kCountModspecBatchDft, kCountModspecLoss, kCountModspecChirp, kCountUnused21, kCountGmmEstep, kCountGmmMstep, kCountGmmPrecisions, kCountUnused25, kCountKmeansSeed, kCountKmeansLloyd, kCountUnused28, kCountPostfilter, kCountUnused30, kCountModspecFilter, kCountUnused32, kCountGmmTraj, kCountKinds };
 void note_launch(int kind);
 // Grow-only scratch, cached per (device, stream, slot): slot 0 generic factor, 1 fastdtw pyramids,
 // 2 generic status, 3 strip records, 4 constant-coefficient kernel (factor table), 5 fastdtw from host costs (D rows, back-pointers), 6 chunked kernel (records, block factors, separator solutions, marks).  Returns nullptr (and sets the error) on failure.
@@ -254,6 +255,10 @@ int launch_gmm_convert(hipStream_t s, const double *x, const double *post, const
 // postfilter.hip: the Merlin post-filter over the frames of a padded batch, one launch (kind kCountPostfilter)
 int launch_postfilter(hipStream_t s, int dtype, const void *mgc, long ld_in, const int32_t *lengths, int B, int Tmax, int D,
                       double alpha, const double *weight, const double *G, int fftlen, void *out, long ld_out);
+// gmm_traj.hip: conditional means and variances of trajectory GMM conversion over a padded batch, one launch (kind kCountGmmTraj)
+int launch_gmm_traj(hipStream_t s, const double *x, long ld_x, const int32_t *lengths, int B, int Tmax, int D, const int32_t *labels,
+                    const double *mu_x, const double *mu_y, const double *A, const double *cvar, int M, double *mean, long ld_mean,
+                    double *var, long ld_var);
 int launch_gather(hipStream_t s, int dtype, const void *src, const int32_t *path, const int32_t *path_len, int N,
                   int Tsrc, int path_stride, int D, int Tout, void *out);
 

@@ -36,6 +36,11 @@
         of mlpg_hip_modspec_filter on the column slice, (b) the same filter composed from modspec with phase, torch arithmetic and
         inv_modspec on float64 copies; milliseconds of both, their ratio, the fraction of the HBM floor (x read plus result written
         at 8 TB/s); also written to profiles/msfilter.json (NNMNKWII_MSFILTER_PROFILE names another file)
+  vc : (only with --only vc) trajectory GMM voice conversion of a corpus: 256 utterances, T in [700, 900], 24 static dims x 3
+        windows (D = 72), M = 64, posterior="device": (a) the loop of MLPG.transform, (b) MLPG.transform_batch, (c) transform_padded
+        on a resident tensor and its three launches, (d) mlpg_hip_gmm_trajectory_stats against gmm_convert(mixture=labels) plus
+        cvar[labels], alternating; medians with their spread, and the stats kernel's bytes over time beside the 8 TB/s peak; also
+        written to profiles/gmm_vc.json (NNMNKWII_GMM_VC_PROFILE names another file)
 
 Each line carries the GPU time (HIP events on the launch stream), the algorithmic bytes, GB/s, and a
 bounded CPU baseline from the oracle on the same host (the checker, timed like bench.py's cpu_baseline).
@@ -865,6 +870,120 @@ def _run(only, quick, device_index):
         emit(**res)
         if not args.quick:
             out_path = os.environ.get("NNMNKWII_MSFILTER_PROFILE") or os.path.join(ROOT, "profiles", "msfilter.json")
+            with open(out_path, "w") as fh:
+                json.dump(res, fh, indent=1, sort_keys=True)
+                fh.write("\n")
+
+    # ---- vc: trajectory GMM voice conversion of a corpus, per utterance and batched; only with --only vc ----
+    if args.only and "vc" in args.only.split(","):
+        from sklearn.mixture import GaussianMixture
+        from nnmnkwii_amd.baseline.gmm import MLPG
+        B, sd, M = (16, 24, 64) if args.quick else (256, 24, 64)
+        D = sd * len(WINDOWS)
+        rng = np.random.RandomState(1234)
+        lens = rng.randint(700, 901, size=B).astype(np.int32)
+        Tmax, frames = int(lens.max()), int(lens.sum())
+        # a joint model built directly (no fit): separated means, well-conditioned full covariances
+        F = 2 * D
+        Q = rng.randn(M, F, F) / np.sqrt(F)
+        cov = Q @ Q.transpose(0, 2, 1) + 0.5 * np.eye(F)
+        gmm = GaussianMixture(n_components=M, covariance_type="full")
+        gmm.weights_, gmm.means_, gmm.covariances_ = np.full(M, 1.0 / M), 1.5 * rng.randn(M, F), 0.5 * (cov + cov.transpose(0, 2, 1))
+        g = MLPG(gmm, windows=WINDOWS, posterior="device")
+        # speech-like label runs: every utterance is a chain of segments of 5 .. 30 frames, each drawn from one component of p(x)
+        chol = np.linalg.cholesky(g.covarXX)
+        utts = []
+        for n in lens:
+            seg = []
+            while sum(seg) < n:
+                seg.append(int(rng.randint(5, 31)))
+            lab = np.repeat(rng.randint(M, size=len(seg)), seg)[:n]
+            utts.append(g.src_means[lab] + np.einsum("nfg,ng->nf", chol[lab], rng.randn(n, D)))
+        X = np.zeros((B, Tmax, D))
+        for i, u in enumerate(utts):
+            X[i, :len(u)] = u
+        Xd, Ld = torch.from_numpy(X).to(dev), torch.from_numpy(lens).to(dev)
+
+        def spread(ts):
+            ts = np.sort(np.asarray(ts, dtype=np.float64))
+            return dict(median_ms=float(np.median(ts)), min_ms=float(ts[0]), max_ms=float(ts[-1]),
+                        q1_ms=float(np.percentile(ts, 25)), q3_ms=float(np.percentile(ts, 75)), n=int(len(ts)))
+
+        def events(fn, steps):
+            evs = []
+            for _ in range(steps):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                evs.append((a, b))
+            torch.cuda.synchronize()
+            return [a.elapsed_time(b) for a, b in evs]
+
+        res = dict(path="gmm-vc-corpus", B=B, Tmax=Tmax, D=D, static_dim=sd, M=M, frames=frames, padded_rows=B * Tmax, posterior="device",
+                   row_tile=_hip.GMM_TRAJ_ROW_TILE, hbm_peak_GBps=HBM_PEAK_GBS)
+        # (a) the parent route: one MLPG.transform per utterance (every length is a shape of its own: the first loop warms them all)
+        ref = [g.transform(u) for u in utts]
+        res["a_transform_loop"] = spread(events(lambda: [g.transform(u) for u in utts], 3))
+        # (b) transform_batch on the same list
+        got = g.transform_batch(utts)
+        res["b_vs_a_rel_err"] = float(max(np.abs(y - r).max() for y, r in zip(got, ref)) / max(np.abs(r).max() for r in ref))
+        g.transform_batch(utts)
+        res["b_transform_batch"] = spread(events(lambda: g.transform_batch(utts), 5))
+        # (c) transform_padded on a resident tensor, and its three launches one by one
+        from nnmnkwii_amd.paramgen import mlpg_batch as _mlpg_batch
+        mu_x, mu_y, A, cvar, px = g._device_model(dev)
+        x2 = Xd.view(B * Tmax, D)
+        for _ in range(3):
+            g.transform_padded(Xd, Ld)
+        res["c_transform_padded"] = spread(events(lambda: g.transform_padded(Xd, Ld), 20))
+        labels = _hip.gmm_estep(x2, *px, want_resp=False, want_labels=True)[2]
+        mean, var = _hip.gmm_trajectory_stats(Xd, Ld, labels, mu_x, mu_y, A, cvar)
+        estep = lambda: _hip.gmm_estep(x2, *px, want_resp=False, want_labels=True)  # noqa: E731
+        stats = lambda: _hip.gmm_trajectory_stats(Xd, Ld, labels, mu_x, mu_y, A, cvar, mean=mean, var=var)  # noqa: E731
+        traj = lambda: _mlpg_batch(mean, var, WINDOWS, Ld)  # noqa: E731
+        for name, fn in (("c_estep", estep), ("c_stats", stats), ("c_mlpg", traj)):
+            for _ in range(3):
+                fn()
+            res[name] = spread(events(fn, 20))
+        # (d) the stats kernel against the composition it replaces, alternating in one run
+        lab64 = labels.to(torch.int64)
+
+        def composed():
+            e = _hip.gmm_convert(x2, None, labels, mu_x, mu_y, A)
+            return e, cvar[lab64]
+
+        e, v = composed()
+        live = (torch.arange(Tmax, device=dev)[None, :] < Ld[:, None]).view(-1)
+        res["d_new_vs_composed_rel"] = float(((mean.view(-1, D) - e)[live].abs().max() / e[live].abs().max()).item())
+        assert torch.equal(var.view(-1, D)[live], v[live])
+        for _ in range(20):     # settle the clocks on both
+            stats()
+            composed()
+        t_new, t_old = [], []
+        for _ in range(24):
+            t_new += events(stats, 1)
+            t_old += events(composed, 1)
+        res["d_stats_kernel"], res["d_composed"] = spread(t_new), spread(t_old)
+        res["d_composed_over_new"] = res["d_composed"]["median_ms"] / res["d_stats_kernel"]["median_ms"]
+        nbytes = float(frames) * (8 * D + 16 * D + 4)
+        res["stats_bytes"] = nbytes
+        res["stats_GBps"] = nbytes / (res["d_stats_kernel"]["median_ms"] * 1e6)
+        res["stats_hbm_peak_frac"] = res["stats_GBps"] / HBM_PEAK_GBS
+        lab_h = labels.view(B * Tmax).cpu().numpy()
+        live_h = live.cpu().numpy()
+        tiles = [np.unique(lab_h[i:i + 64][live_h[i:i + 64]]).size for i in range(0, B * Tmax, 64)]
+        res["distinct_labels_per_tile_mean"] = float(np.mean(tiles))
+        res["distinct_labels_per_tile_max"] = int(np.max(tiles))
+        res["note"] = ("synthetic corpus: a joint model of M separated components built directly, every utterance a chain of 5-30 frame "
+                       "segments drawn from one component each.  HIP-event times around (a) the loop of MLPG.transform over the list "
+                       "(numpy in and out, 3 loops), (b) MLPG.transform_batch on the list (5 calls), (c) transform_padded on a resident "
+                       "tensor (20 calls) and its three launches alone, (d) mlpg_hip_gmm_trajectory_stats against gmm_convert(mixture=labels) "
+                       "plus cvar[labels] by torch over all padded rows, 24 alternating pairs.  Bytes: live rows * (8 D read + 16 D written "
+                       "+ 4 label); A, mu and cvar are not counted.  No time is asserted anywhere")
+        emit(**res)
+        if not args.quick:
+            out_path = os.environ.get("NNMNKWII_GMM_VC_PROFILE") or os.path.join(ROOT, "profiles", "gmm_vc.json")
             with open(out_path, "w") as fh:
                 json.dump(res, fh, indent=1, sort_keys=True)
                 fh.write("\n")
