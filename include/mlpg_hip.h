@@ -85,8 +85,9 @@ const char *mlpg_hip_last_error(void);
  * launches of the typed in-LDS FFT kernel of mlpg_hip_modspec_batch / mlpg_hip_modspec_batch_backward, 18 transforms those two
  * calls sent through the direct transform, 19 launches of the fused loss kernel of mlpg_hip_modspec_loss_step; 20 CALLS of
  * mlpg_hip_modspec / _inv_modspec / _modspec_smoothing / _modspec_backward that the chirp-z kernel served (one per call); 31
- * launches of the kernel of mlpg_hip_modspec_filter; 33 launches of the kernel of mlpg_hip_gmm_trajectory_stats; -1 for any other
- * `kind` (12, 14, 16, 30 and 32 included).
+ * launches of the kernel of mlpg_hip_modspec_filter; 33 launches of the kernel of mlpg_hip_gmm_trajectory_stats; 35
+ * launches of the kernel of mlpg_hip_gv_ascent (one per call, whatever n_iter is), 37 of the kernel of mlpg_hip_gv; -1 for any
+ * other `kind` (12, 14, 16, 30, 32, 34, 36 and 38 included).
  * (Tests use it to assert WHICH kernel / route a call took.) */
 long long mlpg_hip_launch_count(int kind);
 int mlpg_hip_device_count(void);
@@ -766,6 +767,47 @@ int mlpg_hip_gmm_trajectory_stats(int device, void *stream, const double *x,
                                   const double *A, const double *cvar, int M,
                                   double *mean, int64_t ld_mean, double *var,
                                   int64_t ld_var);
+
+/*
+ * Parameter generation with the likelihood of the trajectory's gv (K11, csrc/mlpg_gv.hip; Toda, Black, Tokuda 2007, section
+ * IV; the reference has no such call).  The gv of a system (utterance b, static dim d) with T = live_b frames is the variance
+ * over time v(y) = (1/T) sum_t (y_t - m)^2, m = (1/T) sum_t y_t.  With P = sum_w W_w^T diag(tau_w) W_w and
+ * r = sum_w W_w^T diag(tau_w) mu_w -- what mlpg_hip_forward assembles from mean, var, var_mode and the windows: the same
+ * tau = 1/var per dtype, the same first and last frames -- and omega = omega_scale / (2 T):
+ *   L(y) = omega (-1/2 y^T P y + y^T r) - 1/2 gv_prec[d] (v(y) - gv_mean[d])^2
+ *   g(y) = omega (r - P y) - (2/T) gv_prec[d] (v(y) - gv_mean[d]) (y - m)
+ * and the call runs y <- y + alpha g(y) n_iter times from the start: y_in as given (init 0), or scaled about its mean to the gv
+ * gv_mean[d] (init 1; unchanged where v(y_in) or gv_mean[d] is not positive).  alpha = step where step > 0; else, per system,
+ * alpha = 1 / (omega G + (2/T) gv_prec (|v - gv_mean| + 2 max(v, gv_mean))) at the start, G = max_t sum_j |P_tj| (a bound on the
+ * curvature at the start: a heuristic, not a guarantee).  ONE launch (mlpg_hip_launch_count(35)) for all systems and all
+ * iterations: one wavefront per system, its y, P and r in LDS, the halo by cross-lane moves; no atomics, and a system's bits do
+ * not depend on the rest of the batch.
+ * mean, var, var_mode, lengths, the windows: as mlpg_hip_forward.  y_in, y_out: (B, Tmax, D / num_windows) of `dtype` (float64
+ * arithmetic); y_out == y_in is in place.  Frames at or past live_b of y_out are 0.  gv_mean, gv_prec: device float64
+ * (D / num_windows).  report: device float64 (B * sd * 4): L(start), L(final), v(y_in), v(final); status: device int32 (B * sd):
+ * 0 fine, 1 a non-finite value appeared, 2 L(final) < L(start) - 2^-40 max(|L(start)|, |L(final)|) (no ascent: the step is too
+ * large).  A system with live_b = 0 gets report 0 and status 0.
+ * Limits: window extents <= 1; Tmax <= mlpg_hip_gv_max_frames() (2048); n_iter in [0, 100000]; init 0 or 1; omega_scale > 0.
+ * Anything else is refused with MLPG_HIP_EINVAL and a text that starts "gv_ascent:" before a device is selected, with nothing
+ * launched.  An empty batch returns 0 and touches nothing.
+ */
+int mlpg_hip_gv_max_frames(void);
+int mlpg_hip_gv_ascent(int device, void *stream, int dtype, const void *mean,
+                       const void *var, int var_mode, const int32_t *lengths,
+                       int B, int Tmax, int D, int num_windows,
+                       const int32_t *win_l_h, const int32_t *win_u_h,
+                       const double *win_coef_h, const void *y_in, void *y_out,
+                       const double *gv_mean, const double *gv_prec,
+                       double omega_scale, int n_iter, double step, int init,
+                       double *report, int32_t *status);
+/*
+ * The gv of every (b, d) of a padded batch: x of `dtype`, row (b, t) at x + (b * Tmax + t) * ld_x, ld_x >= D; out float64
+ * (B, D).  Two passes (mean, then squared deviations) over the live frames in frame order; live_b = 0 gives 0.  One launch
+ * (mlpg_hip_launch_count(37)).
+ */
+int mlpg_hip_gv(int device, void *stream, int dtype, const void *x,
+                int64_t ld_x, const int32_t *lengths, int B, int Tmax, int D,
+                double *out);
 
 /*
  * Gather rows along the warping path into zero-padded outputs.  Replaces

@@ -1,11 +1,12 @@
 """nnmnkwii_amd -- MI355X-native MLPG parameter generation and DTW alignment
 behind the Python signatures of r9y9/nnmnkwii's hot path.
 
-    nnmnkwii_amd.paramgen       mlpg, mlpg_grad, unit_variance_mlpg_matrix, reshape_means, ...
+    nnmnkwii_amd.paramgen       mlpg, mlpg_grad, unit_variance_mlpg_matrix, reshape_means, ...;
+                                gv, gv_stats, mlpg_gv, mlpg_gv_batch (MLPG with the likelihood of the trajectory's gv)
     nnmnkwii_amd.autograd       mlpg / MLPG, unit_variance_mlpg / UnitVarianceMLPG (torch, ROCm)
     nnmnkwii_amd.preprocessing  trim_zeros_frames, delta_features, alignment.DTWAligner / IterativeDTWAligner,
                                 modspec / inv_modspec / modspec_smoothing / modspec_smoothing_batch
-    nnmnkwii_amd.baseline.gmm   MLPGBase, MLPG (GMM voice-conversion baseline; caller of paramgen.mlpg)
+    nnmnkwii_amd.baseline.gmm   MLPGBase, MLPG (GMM voice-conversion baseline; caller of paramgen.mlpg; MLPG(..., gv=...) adds the gv stage)
     nnmnkwii_amd.postfilters    merlin_post_filter, merlin_post_filter_batch (mel-cepstral post-filter behind MLPG),
                                 modspec_post_filter, modspec_post_filter_batch, modspec_log_stats, modspec_post_filter_tables
                                 (modulation-spectrum post-filter)

@@ -77,6 +77,9 @@ EXPORTS = (
     "mlpg_hip_modspec_filter_form",
     "mlpg_hip_modspec_filter",
     "mlpg_hip_gmm_trajectory_stats",
+    "mlpg_hip_gv_max_frames",
+    "mlpg_hip_gv_ascent",
+    "mlpg_hip_gv",
 )
 
 
@@ -249,6 +252,12 @@ def lib():
         L.mlpg_hip_gmm_trajectory_stats.restype = ci
         L.mlpg_hip_gmm_trajectory_stats.argtypes = [ci, vp, vp, ctypes.c_int64, vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, ctypes.c_int64,
                                                     vp, ctypes.c_int64]
+        L.mlpg_hip_gv_max_frames.restype = ci
+        L.mlpg_hip_gv_max_frames.argtypes = []
+        L.mlpg_hip_gv_ascent.restype = ci
+        L.mlpg_hip_gv_ascent.argtypes = [ci, vp, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, cd, ci, cd, ci, vp, vp]
+        L.mlpg_hip_gv.restype = ci
+        L.mlpg_hip_gv.argtypes = [ci, vp, ci, vp, ctypes.c_int64, vp, ci, ci, ci, vp]
         _lib = L
     return _lib
 
@@ -1455,6 +1464,63 @@ def gmm_trajectory_stats(x, lengths, labels, mu_x, mu_y, A, cvar, mean=None, var
                                              _p(mu_y), _p(A), _p(cvar), M, _p(mean), lds[1], _p(var), lds[2])
     _check(rc, "mlpg_hip_gmm_trajectory_stats")
     return mean, var
+
+
+def gv_max_frames():
+    """mlpg_hip_gv_max_frames(): the longest padded utterance (Tmax) mlpg_hip_gv_ascent takes."""
+    return lib().mlpg_hip_gv_max_frames()
+
+
+GV_INIT = {"given": 0, "scaled": 1}
+
+
+def gv_ascent(mean, var, windows, y, gv_mean, gv_prec, lengths=None, n_iter=100, step=None, init="scaled", omega_scale=1.0, out=None):
+    """mlpg_hip_gv_ascent on CUDA tensors: mean (B, Tmax, D) float32 / float64 contiguous, var the same shape, (D,) or None, y
+    (B, Tmax, D // num_windows) of mean's dtype: the maximum-likelihood trajectory of (mean, var).  gv_mean, gv_prec: float64
+    (D // num_windows) on the device.  Runs n_iter steps of steepest ascent on the likelihood with the gv term from the start
+    ``init`` ("scaled" or "given"); step None or <= 0: the step the kernel derives per system.  The result goes to ``out``
+    (default: ``y`` itself, in place).  Returns (out, report float64 (B, sd, 4): L(start), L(final), v(y), v(final); status int32
+    (B, sd): 0 fine, 1 non-finite, 2 no ascent), all on the device, enqueued on the current stream.  One launch."""
+    torch = torch_mod()
+    assert mean.is_cuda and mean.dim() == 3 and mean.is_contiguous()
+    B, T, D = mean.shape
+    nw, pl, pu, pc, _keep = _win_args(windows)
+    mode = _var_mode(var, mean, mean.shape, D)
+    _check_lengths(lengths, B, mean.device)
+    sd = D // nw if nw else 0
+    if init not in GV_INIT:
+        raise ValueError("gv_ascent: init must be 'scaled' or 'given', got %r" % (init,))
+    if out is None:
+        out = y
+    for name, t in (("y", y), ("out", out)):
+        if not (t.is_cuda and t.device == mean.device and t.dtype == mean.dtype and tuple(t.shape) == (B, T, sd) and t.is_contiguous()):
+            raise ValueError("gv_ascent: %s must be a contiguous (%d, %d, %d) %s tensor on %s" % (name, B, T, sd, mean.dtype, mean.device))
+    for name, t in (("gv_mean", gv_mean), ("gv_prec", gv_prec)):
+        if not (t.is_cuda and t.device == mean.device and t.dtype == torch.float64 and tuple(t.shape) == (sd,) and t.is_contiguous()):
+            raise ValueError("gv_ascent: %s must be a float64 (%d,) tensor on %s" % (name, sd, mean.device))
+    report = torch.empty((B, sd, 4), dtype=torch.float64, device=mean.device)
+    status = torch.empty((B, sd), dtype=torch.int32, device=mean.device)
+    rc = lib().mlpg_hip_gv_ascent(mean.device.index, _stream(mean.device), _dt(mean), _p(mean), _p(var), mode, _p(lengths), B, T, D, nw,
+                                  pl, pu, pc, _p(y), _p(out), _p(gv_mean), _p(gv_prec), float(omega_scale), int(n_iter),
+                                  -1.0 if step is None else float(step), GV_INIT[init], _p(report), _p(status))
+    _check(rc, "mlpg_hip_gv_ascent")
+    return out, report, status
+
+
+def gv(x, lengths=None):
+    """mlpg_hip_gv: the gv (variance over the live frames) of every (b, d) of a padded batch.  x: (B, Tmax, D) float32 / float64
+    CUDA tensor whose last dimension is contiguous and whose first two are those of a dense (B, Tmax, ld) array (a column slice
+    is fine); lengths: int32 (B,) on the device or None.  Returns float64 (B, D) on the device.  One launch."""
+    torch = torch_mod()
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 3):
+        raise ValueError("gv: x must be a (B, Tmax, D) CUDA tensor")
+    B, T, D = x.shape
+    _check_lengths(lengths, B, x.device)
+    ld = _pf_row_stride(x, B, T, D, "gv")
+    out = torch.empty((B, D), dtype=torch.float64, device=x.device)
+    rc = lib().mlpg_hip_gv(x.device.index, _stream(x.device), _dt(x), _p(x), ld, _p(lengths), B, T, D, _p(out))
+    _check(rc, "mlpg_hip_gv")
+    return out
 
 
 def raise_on_status(status, sd):

@@ -10,7 +10,8 @@ trajectory generation -- the expensive part -- goes to the HIP MLPG kernels thro
 :func:`nnmnkwii_amd.paramgen.mlpg`.  ``transform_batch`` converts a whole list of utterances
 with one launch (what ``IterativeDTWAligner`` calls every iteration).  ``MLPG.transform_padded`` / ``MLPG.transform_batch`` run
 the trajectory conversion of a whole padded batch in three launches -- E-step labels, ``mlpg_hip_gmm_trajectory_stats``, batched
-MLPG -- with the model resident on the device.
+MLPG -- with the model resident on the device.  ``MLPG(..., gv=(gv_mean, gv_var))`` adds the ascent on the likelihood with the gv
+term (``mlpg_hip_gv_ascent``, a fourth launch) to all three.
 """
 import numpy as np
 from scipy import linalg as _sla
@@ -18,6 +19,7 @@ from sklearn.mixture import GaussianMixture
 
 from .. import _hip
 from ..paramgen import mlpg as _mlpg
+from ..paramgen import _mlpg as _pg
 
 
 def _precisions_cholesky_full(covariances):
@@ -153,14 +155,37 @@ class MLPG(MLPGBase):
     ``transform(src)``: per frame the most likely mixture m_t under p(x); E_t and a diagonal
     approximation D_t of the conditional covariance; then ``paramgen.mlpg(E, D, windows)`` on the
     GPU.  Static-only inputs (feature dim == static dim) take the frame-wise path of ``MLPGBase``.
+
+    ``gv=(gv_mean, gv_var)``: mean and variance (static_dim,) of the gv of natural target speech (``paramgen.gv_stats``).  The
+    trajectory of static+delta input is then the one that also maximises the likelihood of its gv (Toda 2007, section IV):
+    ``paramgen.mlpg_gv`` in ``transform``, one more launch in ``transform_padded`` / ``transform_batch`` with the statistics
+    resident on the device beside the model.  ``gv_options``: a dict of ``n_iter``, ``step``, ``init``, ``omega_scale``, ``check``
+    (``paramgen.mlpg_gv_batch``).  Not with ``diff=True``.  The reference has no such option.
     """
 
-    def __init__(self, gmm, windows=None, swap=False, diff=False, *, posterior="sklearn"):
+    def __init__(self, gmm, windows=None, swap=False, diff=False, *, posterior="sklearn", gv=None, gv_options=None):
         super(MLPG, self).__init__(gmm, swap, diff, posterior=posterior)
         if windows is None:
             windows = [(0, 0, np.array([1.0])), (1, 1, np.array([-0.5, 0.0, 0.5]))]
         self.windows = windows
         self.static_dim = gmm.means_.shape[-1] // 2 // len(windows)
+        self.gv = None
+        if gv is None:
+            if gv_options is not None:
+                raise ValueError("gv_options go with gv=(gv_mean, gv_var)")
+        else:
+            if diff:
+                raise ValueError("gv cannot be combined with diff=True: the gv of a spectral difference is not the gv of speech")
+            opts = dict(n_iter=100, step=None, init="scaled", omega_scale=1.0, check=True)
+            unknown = set(gv_options or {}) - set(opts)
+            if unknown:
+                raise ValueError("unknown gv_options: %s" % ", ".join(sorted(unknown)))
+            opts.update(gv_options or {})
+            gv_mean, gv_var = gv
+            self._gv_check = opts.pop("check")
+            gm, _ = _pg._gv_options(gv_mean, gv_var, self.static_dim, **opts)
+            self.gv = (gm, np.asarray(gv_var, dtype=np.float64).ravel())
+            self.gv_options = opts
 
     def transform(self, src):
         if src.shape[1] == self.static_dim:
@@ -172,6 +197,10 @@ class MLPG(MLPGBase):
             E = self._convert(src, mix=mix)                               # eq. 22 / 40
         dg = lambda a: np.diagonal(a, axis1=1, axis2=2)                   # noqa: E731
         Dm = dg(self.covarYY) - dg(self.covarYX) / dg(self.covarXX) * dg(self.covarXY)   # eq. 23, diagonal approx.
+        if self.gv is not None:
+            y = _pg.mlpg_gv_batch(E[None], np.ascontiguousarray(Dm[mix])[None], self.windows, self.gv[0], self.gv[1],
+                                  check=self._gv_check, **self.gv_options)
+            return y[0].astype(E.dtype, copy=False)
         return _mlpg(E, np.ascontiguousarray(Dm[mix]), self.windows)
 
     def _device_model(self, dev):
@@ -185,12 +214,14 @@ class MLPG(MLPGBase):
             dg = lambda a: np.diagonal(a, axis1=1, axis2=2)               # noqa: E731
             cvar = dg(self.covarYY) - dg(self.covarYX) / dg(self.covarXX) * dg(self.covarXY)   # eq. 23, as in transform
             px = _mix._model(self.px, dev) if self.posterior == "device" else None
-            got = cache[dev.index] = (f64(self.src_means), f64(self.tgt_means), f64(self._regression()), f64(cvar), px)
+            gvs = None if self.gv is None else (f64(self.gv[0]), f64(1.0 / self.gv[1]))   # (gv_mean, gv_prec) beside the model
+            got = cache[dev.index] = (f64(self.src_means), f64(self.tgt_means), f64(self._regression()), f64(cvar), px, gvs)
         return got
 
     def transform_padded(self, X, lengths=None):
         """``transform`` over a zero-padded batch: ``X`` (B, Tmax, D) static+delta features, numpy of any float dtype or a
-        float64 CUDA tensor; ``lengths`` (B,) the live frames per utterance (None: all).  Returns (B, Tmax, static_dim) float64
+        float64 CUDA tensor; ``lengths`` (B,) the live frames per utterance (None: all).  With ``gv`` a fourth launch follows
+        (``mlpg_hip_gv_ascent``, in place on the trajectory).  Returns (B, Tmax, static_dim) float64
         of the same kind (what the reference's ``mlpg(E, D, windows)`` returns whatever the dtype of ``src``); frames beyond
         ``lengths`` are zero.  Three launches -- the labels (``posterior="device"``: one E-step over all rows;
         ``"sklearn"``: ``px.predict`` on the live rows on the host, uploaded), ``mlpg_hip_gmm_trajectory_stats``, batched MLPG --
@@ -225,7 +256,7 @@ class MLPG(MLPGBase):
         if B * T == 0:
             y = torch.zeros((B, T, self.static_dim), dtype=torch.float64, device=dev)
             return y if is_tensor else y.cpu().numpy()
-        mu_x, mu_y, A, cvar, px = self._device_model(dev)
+        mu_x, mu_y, A, cvar, px, gvs = self._device_model(dev)
         if self.posterior == "device":
             labels = _hip.gmm_estep(x.view(B * T, D), *px, want_resp=False, want_labels=True)[2]
         else:
@@ -237,6 +268,10 @@ class MLPG(MLPGBase):
             labels = torch.from_numpy(lab).to(dev)
         mean, var = _hip.gmm_trajectory_stats(x, L, labels, mu_x, mu_y, A, cvar)
         y = _mlpg_batch(mean, var, self.windows, L)
+        if gvs is not None:
+            y, report, status = _hip.gv_ascent(mean, var, self.windows, y, gvs[0], gvs[1], L, **self.gv_options)
+            if self._gv_check:
+                _pg.raise_on_gv_status(status, report, self.gv_options["step"])
         return y if is_tensor else y.cpu().numpy()
 
     def transform_batch(self, utterances):

@@ -139,8 +139,9 @@ SideStreams *side_streams(int device);
 // _precisions that launched their kernels (gmm_em.hip); 25 counts nothing and reads -1; 26, 27: calls of mlpg_hip_kmeans_seed_step and
 // _lloyd_step that launched their kernels (kmeans.hip); 28 counts nothing and reads -1; 29: calls of mlpg_hip_merlin_post_filter that
 // launched (postfilter.hip); 30 counts nothing and reads -1; 31: launches of the kernel of mlpg_hip_modspec_filter (modspec_filter.hip); 32 counts nothing and reads -1; 33: launches of the
-// kernel of mlpg_hip_gmm_trajectory_stats (gmm_traj.hip))
-enum { kCountGeneric = 0, kCountWave, kCountStrip, kCountStripMulti, kCountConst, kCountFused, kCountChunk, kCountFir, kCountConstMulti, kCountStripTr, kCountHostSmall, kCountHostSmallDirect, kCountUnused12, kCountVarGrad, kCountUnused14, kCountStreamsBwd, kCountUnused16, kCountModspecBatch, kCountModspecBatchDft, kCountModspecLoss, kCountModspecChirp, kCountUnused21, kCountGmmEstep, kCountGmmMstep, kCountGmmPrecisions, kCountUnused25, kCountKmeansSeed, kCountKmeansLloyd, kCountUnused28, kCountPostfilter, kCountUnused30, kCountModspecFilter, kCountUnused32, kCountGmmTraj, kCountKinds };
+// kernel of mlpg_hip_gmm_trajectory_stats (gmm_traj.hip); 34 and 36 count nothing and read -1; 35: launches of the kernel of
+// mlpg_hip_gv_ascent, 37: of mlpg_hip_gv (mlpg_gv.hip))
+enum { kCountGeneric = 0, kCountWave, kCountStrip, kCountStripMulti, kCountConst, kCountFused, kCountChunk, kCountFir, kCountConstMulti, kCountStripTr, kCountHostSmall, kCountHostSmallDirect, kCountUnused12, kCountVarGrad, kCountUnused14, kCountStreamsBwd, kCountUnused16, kCountModspecBatch, kCountModspecBatchDft, kCountModspecLoss, kCountModspecChirp, kCountUnused21, kCountGmmEstep, kCountGmmMstep, kCountGmmPrecisions, kCountUnused25, kCountKmeansSeed, kCountKmeansLloyd, kCountUnused28, kCountPostfilter, kCountUnused30, kCountModspecFilter, kCountUnused32, kCountGmmTraj, kCountUnused34, kCountGvAscent, kCountUnused36, kCountGv, kCountKinds };
 void note_launch(int kind);
 // Grow-only scratch, cached per (device, stream, slot): slot 0 generic factor, 1 fastdtw pyramids,
 // 2 generic status, 3 strip records, 4 constant-coefficient kernel (factor table), 5 fastdtw from host costs (D rows, back-pointers), 6 chunked kernel (records, block factors, separator solutions, marks).  Returns nullptr (and sets the error) on failure.

@@ -19,6 +19,10 @@ __all__ = [
     "full_window_mat",
     "mlpg_batch",
     "multi_stream_mlpg",
+    "gv",
+    "gv_stats",
+    "mlpg_gv",
+    "mlpg_gv_batch",
 ]
 
 
@@ -303,6 +307,137 @@ def mlpg_grad(mean_frames, variance_frames, windows, grad_output):
     if status.any():
         _raise_host_status(status)
     return grad[0]
+
+
+# ---- MLPG with the likelihood of the trajectory's gv (Toda, Black, Tokuda 2007, section IV) --------------------
+def _as_device_batch(X, dev=None):
+    """numpy or tensor, float32 / float64 -> (CUDA tensor, was it numpy)."""
+    torch = _hip.torch_mod()
+    is_np = not torch.is_tensor(X)
+    dev = _hip.require_gpu(dev if is_np or not X.is_cuda else X.device)
+    return (torch.from_numpy(np.ascontiguousarray(_as_float(X))).to(dev) if is_np else X.to(dev)), is_np
+
+
+def _device_lengths(lengths, dev):
+    if lengths is None:
+        return None
+    torch = _hip.torch_mod()
+    return torch.as_tensor(np.asarray(lengths) if not torch.is_tensor(lengths) else lengths).to(device=dev, dtype=torch.int32).contiguous()
+
+
+def gv(X, lengths=None):
+    """The gv of features: the variance over time of each dimension of one utterance.  ``X`` (T, sd) -> (sd,), or a zero-padded
+    batch (B, Tmax, sd) with ``lengths`` (B,) -> (B, sd); float64, numpy for numpy input, a CUDA tensor for a CUDA tensor.  An
+    utterance without live frames gives 0.  One launch of ``mlpg_hip_gv``."""
+    x, is_np = _as_device_batch(X)
+    two_d = x.dim() == 2
+    if two_d:
+        if lengths is not None:
+            raise ValueError("gv: lengths go with a padded (B, Tmax, sd) batch")
+        x = x[None]
+    if x.dim() != 3:
+        raise ValueError("gv takes (T, sd) features or a padded (B, Tmax, sd) batch")
+    out = _hip.gv(x, _device_lengths(lengths, x.device))
+    if two_d:
+        out = out[0]
+    return out.cpu().numpy() if is_np else out
+
+
+def gv_stats(X, lengths):
+    """(gv_mean, gv_var): float64 (sd,) mean and variance of the gv over the utterances of a padded batch that have live frames
+    (``lengths > 0``) -- what ``mlpg_gv`` takes.  The gv comes from the device (``gv``), the two moments are taken on the host."""
+    g = gv(X, lengths)
+    g = g if isinstance(g, np.ndarray) else g.cpu().numpy()
+    keep = np.asarray(lengths if not hasattr(lengths, "cpu") else lengths.cpu().numpy()) > 0
+    if not keep.any():
+        raise ValueError("gv_stats: no utterance has live frames")
+    return g[keep].mean(axis=0), g[keep].var(axis=0)
+
+
+def _gv_options(gv_mean, gv_var, sd, n_iter, step, init, omega_scale):
+    """The checks of mlpg_gv / mlpg_gv_batch that need no device: ValueError, or (gv_mean, gv_prec) as float64 (sd,) arrays."""
+    gm, gvv = np.asarray(gv_mean, dtype=np.float64).ravel(), np.asarray(gv_var, dtype=np.float64).ravel()
+    if gm.shape != (sd,) or gvv.shape != (sd,):
+        raise ValueError("gv_mean and gv_var must have one entry per static dimension (%d), got %d and %d" % (sd, gm.size, gvv.size))
+    if not (gvv > 0).all():
+        raise ValueError("gv_var must be positive (entry %d is %r)" % (int(np.flatnonzero(~(gvv > 0))[0]), float(gvv[~(gvv > 0)][0])))
+    if init not in _hip.GV_INIT:
+        raise ValueError("init must be 'scaled' or 'given', got %r" % (init,))
+    if not (0 <= int(n_iter) <= 100000):
+        raise ValueError("n_iter must be in [0, 100000], got %r" % (n_iter,))
+    if not (omega_scale > 0 and np.isfinite(omega_scale)):
+        raise ValueError("omega_scale must be positive and finite, got %r" % (omega_scale,))
+    if step is not None and not np.isfinite(step):
+        raise ValueError("step must be finite (None or <= 0: the derived step), got %r" % (step,))
+    return gm, 1.0 / gvv
+
+
+def raise_on_gv_status(status, report, step):
+    """ValueError for the first (utterance, dim) whose ascent failed: status 1 (non-finite) or 2 (no ascent)."""
+    st = status.cpu().numpy()
+    bad = np.argwhere(st != 0)
+    if len(bad):
+        b, d = (int(i) for i in bad[0])
+        if st[b, d] == 1:
+            raise ValueError("mlpg_gv: a non-finite value appeared in utterance %d, dim %d" % (b, d))
+        rep = report[b, d].cpu().numpy()
+        raise ValueError("mlpg_gv: no ascent in utterance %d, dim %d (the likelihood went from %r to %r): the step %s is too large"
+                         % (b, d, float(rep[0]), float(rep[1]), "derived by the kernel" if step is None or step <= 0 else repr(step)))
+
+
+def mlpg_gv_batch(means, variances, windows, gv_mean, gv_var, lengths=None, n_iter=100, step=None, init="scaled", omega_scale=1.0,
+                  algo=_hip.ALGO_AUTO, check=True, return_report=False, device=None):
+    """MLPG that also maximises the likelihood of the trajectory's gv, over a zero-padded ``(B, Tmax, D)`` batch: the plain
+    maximum-likelihood trajectory (``mlpg_batch``: any route) followed, in place, by ``n_iter`` steps of steepest ascent on
+    ``L(y) = omega (-1/2 y'Py + y'r) - 1/2 (v(y) - gv_mean)^2 / gv_var``, ``omega = omega_scale / (2 T)``, in ONE further launch
+    (``mlpg_hip_gv_ascent``).  ``gv_mean``, ``gv_var`` (static_dim,): mean and variance of the gv of natural speech
+    (``gv_stats``); the gv density is diagonal.  ``init``: "scaled" (the trajectory scaled about its mean to the gv ``gv_mean``;
+    with ``n_iter=0`` the familiar variance-scaling filter) or "given"; ``step``: None for the step the kernel derives per system.
+    Inputs and result as ``mlpg_batch`` (numpy -> numpy, CUDA tensor -> CUDA tensor, the dtype of the means).  ``check``: raise
+    ``LinAlgError`` as ``mlpg_batch`` does and ``ValueError`` where the ascent met a non-finite value or did not ascend.
+    ``return_report``: also return ``(report (B, sd, 4): L(start), L(final), v(ML trajectory), v(final); status (B, sd))``.
+    Window extents of at most 1 and ``Tmax <= _hip.gv_max_frames()``."""
+    nw = _hip._nw(windows)
+    D = np.shape(means)[-1]
+    if nw < 1 or D % nw:
+        raise ValueError("D = %d is not a multiple of the %d windows" % (D, nw))
+    gm, gp = _gv_options(gv_mean, gv_var, D // nw, n_iter, step, init, omega_scale)
+    torch = _hip.torch_mod()
+    m, is_np = _as_device_batch(means, device)
+    dev = m.device
+    m = m.contiguous()
+    assert m.dim() == 3
+    out_dtype = m.dtype
+    v = None
+    if variances is not None:
+        v = (variances if torch.is_tensor(variances) else
+             torch.from_numpy(np.ascontiguousarray(_as_float(variances)))).to(dev).contiguous()
+        m, v = _match_dtypes(m, v)
+    L = _device_lengths(lengths, dev)
+    y = mlpg_batch(m, v, windows, L, algo=algo, check=check)
+    y, report, status = _hip.gv_ascent(m, v, windows, y, torch.from_numpy(gm).to(dev), torch.from_numpy(gp).to(dev), L,
+                                       n_iter=n_iter, step=step, init=init, omega_scale=omega_scale)
+    if check:
+        raise_on_gv_status(status, report, step)
+    if y.dtype != out_dtype:
+        y = y.to(out_dtype)
+    if is_np:
+        y, report, status = y.cpu().numpy(), report.cpu().numpy(), status.cpu().numpy()
+    return (y, report, status) if return_report else y
+
+
+def mlpg_gv(mean_frames, variance_frames, windows, gv_mean, gv_var, n_iter=100, step=None, init="scaled", omega_scale=1.0):
+    """``mlpg`` followed by the ascent on the likelihood with the gv term, ``(T, D) -> (T, static_dim)``: see ``mlpg_gv_batch``.
+    Arguments and result as ``mlpg`` (numpy, the dtype of ``mean_frames``; per-frame ``(T, D)`` or global ``(D,)`` variances)."""
+    mean_frames = np.asarray(mean_frames)
+    variance_frames = np.asarray(variance_frames)
+    dtype = mean_frames.dtype
+    T, D = mean_frames.shape
+    if not (variance_frames.ndim == 1 and variance_frames.shape[0] == D):
+        assert mean_frames.shape == variance_frames.shape
+        variance_frames = variance_frames[None]
+    y = mlpg_gv_batch(mean_frames[None], variance_frames, windows, gv_mean, gv_var, None, n_iter, step, init, omega_scale)
+    return y[0].astype(dtype, copy=False)
 
 
 # registry of MLPG matrices handed out by unit_variance_mlpg_matrix, so that

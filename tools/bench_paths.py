@@ -41,6 +41,10 @@
         on a resident tensor and its three launches, (d) mlpg_hip_gmm_trajectory_stats against gmm_convert(mixture=labels) plus
         cvar[labels], alternating; medians with their spread, and the stats kernel's bytes over time beside the 8 TB/s peak; also
         written to profiles/gmm_vc.json (NNMNKWII_GMM_VC_PROFILE names another file)
+  gv : (only with --only gv) MLPG with the gv likelihood on the corpus of vc, 100 iterations: the one launch of mlpg_hip_gv_ascent
+        against the same iteration composed from torch operations on resident tensors (banded product by shifted slices),
+        alternating; medians with [min, max], the ratio and the agreement of the two routes; also written to
+        profiles/gvmlpg.json (NNMNKWII_GVMLPG_PROFILE names another file)
 
 Each line carries the GPU time (HIP events on the launch stream), the algorithmic bytes, GB/s, and a
 bounded CPU baseline from the oracle on the same host (the checker, timed like bench.py's cpu_baseline).
@@ -301,6 +305,60 @@ def literal_calls(emit, quick=False, long_reference_backward=True):
     emit(path="lit-dtw-DTWAligner.transform-one-pair", us_per_call=us, us_per_call_min=us_min, cpu_us_per_call=cus,
          cpu_kind="oracle/dtw_oracle.c through oracle/dtw.py dtw_align (C restatement of fastdtw; the reference's pure-Python fastdtw package is absent)",
          aligned_arrays_equal_oracle=same, Tx=a, Ty=b, D=25)
+
+
+def spread(ts):
+    ts = np.sort(np.asarray(ts, dtype=np.float64))
+    return dict(median_ms=float(np.median(ts)), min_ms=float(ts[0]), max_ms=float(ts[-1]),
+                q1_ms=float(np.percentile(ts, 25)), q3_ms=float(np.percentile(ts, 75)), n=int(len(ts)))
+
+
+def events(fn, steps):
+    """HIP-event milliseconds of `steps` calls of fn, one pair of events per call."""
+    import torch
+    evs = []
+    for _ in range(steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        evs.append((a, b))
+    torch.cuda.synchronize()
+    return [a.elapsed_time(b) for a, b in evs]
+
+
+def vc_corpus(quick, dev):
+    """The synthetic corpus of --only vc and --only gv: 256 utterances (16 with --quick), T in [700, 900], 24 static dims x 3
+    windows, a joint model of 64 separated components built directly.  Returns (g, utts, X, lens, Xd, Ld, B, sd, M, D, Tmax, frames)."""
+    import torch
+    from sklearn.mixture import GaussianMixture
+    from nnmnkwii_amd.baseline.gmm import MLPG
+    B, sd, M = (16, 24, 64) if quick else (256, 24, 64)
+    D = sd * len(WINDOWS)
+    rng = np.random.RandomState(1234)
+    lens = rng.randint(700, 901, size=B).astype(np.int32)
+    Tmax, frames = int(lens.max()), int(lens.sum())
+    # a joint model built directly (no fit): separated means, well-conditioned full covariances
+    F = 2 * D
+    Q = rng.randn(M, F, F) / np.sqrt(F)
+    cov = Q @ Q.transpose(0, 2, 1) + 0.5 * np.eye(F)
+    gmm = GaussianMixture(n_components=M, covariance_type="full")
+    gmm.weights_, gmm.means_, gmm.covariances_ = np.full(M, 1.0 / M), 1.5 * rng.randn(M, F), 0.5 * (cov + cov.transpose(0, 2, 1))
+    g = MLPG(gmm, windows=WINDOWS, posterior="device")
+    # speech-like label runs: every utterance is a chain of segments of 5 .. 30 frames, each drawn from one component of p(x)
+    chol = np.linalg.cholesky(g.covarXX)
+    utts = []
+    for n in lens:
+        seg = []
+        while sum(seg) < n:
+            seg.append(int(rng.randint(5, 31)))
+        lab = np.repeat(rng.randint(M, size=len(seg)), seg)[:n]
+        utts.append(g.src_means[lab] + np.einsum("nfg,ng->nf", chol[lab], rng.randn(n, D)))
+    X = np.zeros((B, Tmax, D))
+    for i, u in enumerate(utts):
+        X[i, :len(u)] = u
+    Xd, Ld = torch.from_numpy(X).to(dev), torch.from_numpy(lens).to(dev)
+    return g, utts, X, lens, Xd, Ld, B, sd, M, D, Tmax, frames
 
 
 def main():
@@ -876,50 +934,7 @@ def _run(only, quick, device_index):
 
     # ---- vc: trajectory GMM voice conversion of a corpus, per utterance and batched; only with --only vc ----
     if args.only and "vc" in args.only.split(","):
-        from sklearn.mixture import GaussianMixture
-        from nnmnkwii_amd.baseline.gmm import MLPG
-        B, sd, M = (16, 24, 64) if args.quick else (256, 24, 64)
-        D = sd * len(WINDOWS)
-        rng = np.random.RandomState(1234)
-        lens = rng.randint(700, 901, size=B).astype(np.int32)
-        Tmax, frames = int(lens.max()), int(lens.sum())
-        # a joint model built directly (no fit): separated means, well-conditioned full covariances
-        F = 2 * D
-        Q = rng.randn(M, F, F) / np.sqrt(F)
-        cov = Q @ Q.transpose(0, 2, 1) + 0.5 * np.eye(F)
-        gmm = GaussianMixture(n_components=M, covariance_type="full")
-        gmm.weights_, gmm.means_, gmm.covariances_ = np.full(M, 1.0 / M), 1.5 * rng.randn(M, F), 0.5 * (cov + cov.transpose(0, 2, 1))
-        g = MLPG(gmm, windows=WINDOWS, posterior="device")
-        # speech-like label runs: every utterance is a chain of segments of 5 .. 30 frames, each drawn from one component of p(x)
-        chol = np.linalg.cholesky(g.covarXX)
-        utts = []
-        for n in lens:
-            seg = []
-            while sum(seg) < n:
-                seg.append(int(rng.randint(5, 31)))
-            lab = np.repeat(rng.randint(M, size=len(seg)), seg)[:n]
-            utts.append(g.src_means[lab] + np.einsum("nfg,ng->nf", chol[lab], rng.randn(n, D)))
-        X = np.zeros((B, Tmax, D))
-        for i, u in enumerate(utts):
-            X[i, :len(u)] = u
-        Xd, Ld = torch.from_numpy(X).to(dev), torch.from_numpy(lens).to(dev)
-
-        def spread(ts):
-            ts = np.sort(np.asarray(ts, dtype=np.float64))
-            return dict(median_ms=float(np.median(ts)), min_ms=float(ts[0]), max_ms=float(ts[-1]),
-                        q1_ms=float(np.percentile(ts, 25)), q3_ms=float(np.percentile(ts, 75)), n=int(len(ts)))
-
-        def events(fn, steps):
-            evs = []
-            for _ in range(steps):
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                fn()
-                b.record()
-                evs.append((a, b))
-            torch.cuda.synchronize()
-            return [a.elapsed_time(b) for a, b in evs]
-
+        g, utts, X, lens, Xd, Ld, B, sd, M, D, Tmax, frames = vc_corpus(args.quick, dev)
         res = dict(path="gmm-vc-corpus", B=B, Tmax=Tmax, D=D, static_dim=sd, M=M, frames=frames, padded_rows=B * Tmax, posterior="device",
                    row_tile=_hip.GMM_TRAJ_ROW_TILE, hbm_peak_GBps=HBM_PEAK_GBS)
         # (a) the parent route: one MLPG.transform per utterance (every length is a shape of its own: the first loop warms them all)
@@ -932,7 +947,7 @@ def _run(only, quick, device_index):
         res["b_transform_batch"] = spread(events(lambda: g.transform_batch(utts), 5))
         # (c) transform_padded on a resident tensor, and its three launches one by one
         from nnmnkwii_amd.paramgen import mlpg_batch as _mlpg_batch
-        mu_x, mu_y, A, cvar, px = g._device_model(dev)
+        mu_x, mu_y, A, cvar, px = g._device_model(dev)[:5]
         x2 = Xd.view(B * Tmax, D)
         for _ in range(3):
             g.transform_padded(Xd, Ld)
@@ -984,6 +999,111 @@ def _run(only, quick, device_index):
         emit(**res)
         if not args.quick:
             out_path = os.environ.get("NNMNKWII_GMM_VC_PROFILE") or os.path.join(ROOT, "profiles", "gmm_vc.json")
+            with open(out_path, "w") as fh:
+                json.dump(res, fh, indent=1, sort_keys=True)
+                fh.write("\n")
+
+    # ---- gv: the ascent on the likelihood with the gv term, one launch against the iteration composed from torch operations ----
+    if args.only and "gv" in args.only.split(","):
+        from nnmnkwii_amd.paramgen import mlpg_batch as _mlpg_batch
+        g, utts, X, lens, Xd, Ld, B, sd, M, D, Tmax, frames = vc_corpus(args.quick, dev)
+        n_iter = 100
+        mu_x, mu_y, A, cvar, px = g._device_model(dev)[:5]
+        labels = _hip.gmm_estep(Xd.view(B * Tmax, D), *px, want_resp=False, want_labels=True)[2]
+        mean, var = _hip.gmm_trajectory_stats(Xd, Ld, labels, mu_x, mu_y, A, cvar)
+        y0 = _mlpg_batch(mean, var, WINDOWS, Ld)
+        gv0 = _hip.gv(y0, Ld)
+        gv_mean = 1.8 * gv0.mean(dim=0)                 # statistics above the gv of the over-smoothed trajectories
+        gv_prec = 1.0 / (0.2 * gv_mean) ** 2
+        # the composed route's tables, built once outside the timed region: the band columns of P and r by shifted slices
+        Tf = Ld.to(torch.float64)[:, None, None]
+        tt = torch.arange(Tmax, device=dev)[None, :, None]
+        live = (tt < Ld[:, None, None]).to(torch.float64)
+
+        def shift(x, o):                                 # shift(x, o)[f] = x[f - o], 0 outside
+            z = torch.zeros_like(x)
+            if o == 0:
+                z.copy_(x)
+            elif o > 0:
+                z[:, o:] = x[:, :-o]
+            else:
+                z[:, :o] = x[:, -o:]
+            return z
+
+        pk = [torch.zeros((B, Tmax, sd), dtype=torch.float64, device=dev) for _ in range(3)]
+        r = torch.zeros((B, Tmax, sd), dtype=torch.float64, device=dev)
+        for w, (l, u, c) in enumerate(WINDOWS):
+            tau = live / var[:, :, w * sd:(w + 1) * sd]
+            if w:
+                tau = tau * ((tt >= 1) & (tt < Ld[:, None, None] - 1)).to(torch.float64)
+            mu = mean[:, :, w * sd:(w + 1) * sd]
+            for o in range(u, -l - 1, -1):
+                a = float(c[l + o]) * shift(tau, o)
+                r += a * shift(mu, o)
+                for k in range(3):
+                    if l + o + k <= l + u:
+                        pk[k] += a * float(c[l + o + k]) * shift(live, -k)
+        Pd, P1, P2 = pk
+        omega = 1.0 / (2.0 * Tf)
+
+        def band(y):
+            py = Pd * y
+            py[:, :-1] += P1[:, :-1] * y[:, 1:]
+            py[:, :-2] += P2[:, :-2] * y[:, 2:]
+            py[:, 1:] += P1[:, :-1] * y[:, :-1]
+            py[:, 2:] += P2[:, :-2] * y[:, :-2]
+            return py
+
+        def mean_var(y):
+            m = y.sum(dim=1, keepdim=True) / Tf
+            e = (y - m) * live
+            return m, (e * e).sum(dim=1, keepdim=True) / Tf
+
+        rows = Pd.abs() + P1.abs() + P2.abs() + shift(P1, 1).abs() + shift(P2, 2).abs()
+        Gmax = rows.max(dim=1, keepdim=True)[0]
+
+        def composed():
+            y = y0.clone()
+            m, v = mean_var(y)
+            y = (m + torch.sqrt(gv_mean / v) * (y - m)) * live
+            m, v = mean_var(y)
+            alpha = 1.0 / (omega * Gmax + 2.0 / Tf * gv_prec * ((v - gv_mean).abs() + 2.0 * torch.maximum(v, gv_mean.expand_as(v))))
+            for _ in range(n_iter):
+                grad = omega * (r - band(y)) - 2.0 / Tf * gv_prec * (v - gv_mean) * (y - m)
+                y = (y + alpha * grad) * live
+                m, v = mean_var(y)
+            return y
+
+        ybuf = torch.empty_like(y0)
+
+        def kernel():
+            return _hip.gv_ascent(mean, var, WINDOWS, y0, gv_mean, gv_prec, Ld, n_iter=n_iter, out=ybuf)
+
+        yk, report, status = kernel()
+        yc = composed()
+        res = dict(path="gv-ascent-corpus", B=B, Tmax=Tmax, D=D, static_dim=sd, frames=frames, n_iter=n_iter, systems=B * sd,
+                   status_nonzero=int((status != 0).sum().item()),
+                   kernel_vs_composed_rel=float(((yk - yc).abs().max() / yc.abs().max()).item()),
+                   gv_ml_over_mean=float((gv0.mean(dim=0) / gv_mean).mean().item()),
+                   gv_final_over_mean=float((report[:, :, 3].mean(dim=0) / gv_mean).mean().item()))
+        for _ in range(3):                               # settle the clocks on both
+            kernel()
+        composed()
+        t_new, t_old = [], []
+        for _ in range(4 if args.quick else 12):
+            t_new += events(kernel, 1)
+            t_old += events(composed, 1)
+        res["kernel"], res["composed"] = spread(t_new), spread(t_old)
+        res["composed_over_kernel"] = res["composed"]["median_ms"] / res["kernel"]["median_ms"]
+        res["note"] = ("the corpus of --only vc; mean and var from mlpg_hip_gmm_trajectory_stats, y0 from batched MLPG, the gv statistics "
+                       "1.8 x the mean gv of y0 with a standard deviation of 0.2 of that.  HIP-event times, alternating pairs, of ONE launch "
+                       "of mlpg_hip_gv_ascent (scaled start, derived step, 100 iterations, out of place) against the same iteration composed "
+                       "from torch operations on resident float64 tensors (the band columns of P, r and the row sums built once outside the "
+                       "timed region; the banded product by shifted slices).  The composed route is the yardstick: the parent has no such "
+                       "capability.  No counters were collected; no time is asserted anywhere")
+        emit(**res)
+        if not args.quick:
+            out_path = os.environ.get("NNMNKWII_GVMLPG_PROFILE") or os.path.join(ROOT, "profiles", "gvmlpg.json")
             with open(out_path, "w") as fh:
                 json.dump(res, fh, indent=1, sort_keys=True)
                 fh.write("\n")
