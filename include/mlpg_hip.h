@@ -86,8 +86,9 @@ const char *mlpg_hip_last_error(void);
  * calls sent through the direct transform, 19 launches of the fused loss kernel of mlpg_hip_modspec_loss_step; 20 CALLS of
  * mlpg_hip_modspec / _inv_modspec / _modspec_smoothing / _modspec_backward that the chirp-z kernel served (one per call); 31
  * launches of the kernel of mlpg_hip_modspec_filter; 33 launches of the kernel of mlpg_hip_gmm_trajectory_stats; 35
- * launches of the kernel of mlpg_hip_gv_ascent (one per call, whatever n_iter is), 37 of the kernel of mlpg_hip_gv; -1 for any
- * other `kind` (12, 14, 16, 30, 32, 34, 36 and 38 included).
+ * launches of the kernel of mlpg_hip_gv_ascent (one per call, whatever n_iter is), 37 of the kernel of mlpg_hip_gv; 39 CALLS of
+ * mlpg_hip_column_stats that launched, 41 launches of the kernel of mlpg_hip_column_affine; -1 for any other `kind` (12, 14, 16,
+ * 30, 32, 34, 36, 38, 40 and 42 included).
  * (Tests use it to assert WHICH kernel / route a call took.) */
 long long mlpg_hip_launch_count(int kind);
 int mlpg_hip_device_count(void);
@@ -808,6 +809,49 @@ int mlpg_hip_gv_ascent(int device, void *stream, int dtype, const void *mean,
 int mlpg_hip_gv(int device, void *stream, int dtype, const void *x,
                 int64_t ld_x, const int32_t *lengths, int B, int Tmax, int D,
                 double *out);
+
+/*
+ * Corpus normalisation (csrc/colstats.hip; tools/norm_model.py is the executable specification).
+ *
+ * mlpg_hip_column_stats replaces the reference's host loops preprocessing/generic.py:496-549 (meanvar: one scikit-learn
+ * _incremental_mean_and_var call per utterance), :552-602 (meanstd) and :605-636 (minmax: a second pass) with ONE pass over a
+ * padded batch: x of `dtype`, row (b, t) at x + (b * Tmax + t) * ld_x, ld_x >= D (a column slice of a wider array is fine);
+ * lengths: device int32 (B) or NULL; frames at or past live_b = min(max(lengths[b], 0), Tmax) are never read.  state_in,
+ * state_out: device float64 (5, D), rows count, mean, M2 = sum (x - mean)^2, min, max over every live frame seen so far;
+ * state_in NULL is the empty state (0, 0, 0, +inf, -inf), state_in == state_out is allowed, and the incoming state is merged
+ * first.  Arithmetic is float64.  A column that is constant over the live frames gives mean == the constant and M2 == 0
+ * exactly; a column with a non-finite live value gives mean = M2 = NaN; min and max propagate NaN as np.minimum / np.maximum.
+ * A workgroup takes MLPG_HIP_COLSTATS_BLOCK_ROWS frames of one utterance in chunks of MLPG_HIP_COLSTATS_CHUNK_ROWS and writes
+ * its partial state to `workspace` (device memory, at least mlpg_hip_column_stats_workspace(B, Tmax, D) bytes, 8-byte
+ * aligned); a second small launch merges the partials in a fixed order.  No atomics, no synchronisation with the host, and a
+ * division of the work that depends on (B, Tmax, D) alone: the same bits on every call and every device, and the call can be
+ * captured into a graph.  B == 0 or Tmax == 0 with D > 0 still writes state_out (state_in, or the empty state); D == 0
+ * returns 0.  mlpg_hip_launch_count(39) counts the calls that launched.
+ * mlpg_hip_column_stats_workspace: host code, touches no device; -1 if a size is negative or the byte count does not fit.
+ *
+ * mlpg_hip_column_affine replaces :639-665 (scale), :668-684 (inv_scale), :734-786 (minmax_scale) and :789-828
+ * (inv_minmax_scale): mode 0  y = (x - c[d]) / a[d],  mode 1  y = a[d] * x + c[d]  in float64 with separate operations
+ * (float64 results equal numpy's bit for bit), rounded once to out_dtype.  a, c: device float64 (D).  x of in_dtype with row
+ * stride ld_x, y of out_dtype with row stride ld_y, both >= D; y == x (one dtype, equal strides) is in place.  Rows at or past
+ * live_b are never read and come out as exact zeros in columns 0 .. D - 1; columns past D are never touched.  One launch
+ * (mlpg_hip_launch_count(41)).  Apart from y == x, the elements of y must not overlap those of x (other columns of the same
+ * wide array are fine): that is the caller's duty, the call cannot tell such slices from overlapping ones and checks nothing.
+ *
+ * Refused with MLPG_HIP_EINVAL before a device is selected, with nothing launched, in a text that starts "column_stats:" /
+ * "column_affine:": a dtype other than MLPG_HIP_F32 / _F64, a negative size, a row stride below D, a device outside [0, 16), a
+ * required pointer that is NULL, a workspace that is too small or not 8-byte aligned, a mode other than 0 or 1.
+ */
+#define MLPG_HIP_COLSTATS_CHUNK_ROWS 16
+#define MLPG_HIP_COLSTATS_BLOCK_ROWS 512
+int64_t mlpg_hip_column_stats_workspace(int B, int Tmax, int D);
+int mlpg_hip_column_stats(int device, void *stream, int dtype, const void *x,
+                          int64_t ld_x, const int32_t *lengths, int B, int Tmax,
+                          int D, const double *state_in, double *state_out,
+                          void *workspace, int64_t workspace_bytes);
+int mlpg_hip_column_affine(int device, void *stream, int in_dtype,
+                           int out_dtype, int mode, const void *x, int64_t ld_x,
+                           void *y, int64_t ld_y, const int32_t *lengths, int B,
+                           int Tmax, int D, const double *a, const double *c);
 
 /*
  * Gather rows along the warping path into zero-padded outputs.  Replaces

@@ -80,6 +80,9 @@ EXPORTS = (
     "mlpg_hip_gv_max_frames",
     "mlpg_hip_gv_ascent",
     "mlpg_hip_gv",
+    "mlpg_hip_column_stats_workspace",
+    "mlpg_hip_column_stats",
+    "mlpg_hip_column_affine",
 )
 
 
@@ -258,6 +261,14 @@ def lib():
         L.mlpg_hip_gv_ascent.argtypes = [ci, vp, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, cd, ci, cd, ci, vp, vp]
         L.mlpg_hip_gv.restype = ci
         L.mlpg_hip_gv.argtypes = [ci, vp, ci, vp, ctypes.c_int64, vp, ci, ci, ci, vp]
+        # preprocessing/generic.py:496-636 (meanvar, meanstd, minmax) in one pass
+        L.mlpg_hip_column_stats_workspace.restype = ctypes.c_int64
+        L.mlpg_hip_column_stats_workspace.argtypes = [ci, ci, ci]
+        L.mlpg_hip_column_stats.restype = ci
+        L.mlpg_hip_column_stats.argtypes = [ci, vp, ci, vp, ctypes.c_int64, vp, ci, ci, ci, vp, vp, vp, ctypes.c_int64]
+        # preprocessing/generic.py:639-684 (scale, inv_scale) and :734-828 (minmax_scale, inv_minmax_scale)
+        L.mlpg_hip_column_affine.restype = ci
+        L.mlpg_hip_column_affine.argtypes = [ci, vp, ci, ci, ci, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ci, ci, ci, vp, vp]
         _lib = L
     return _lib
 
@@ -1520,6 +1531,72 @@ def gv(x, lengths=None):
     out = torch.empty((B, D), dtype=torch.float64, device=x.device)
     rc = lib().mlpg_hip_gv(x.device.index, _stream(x.device), _dt(x), _p(x), ld, _p(lengths), B, T, D, _p(out))
     _check(rc, "mlpg_hip_gv")
+    return out
+
+
+COLSTATS_CHUNK_ROWS = 16        # MLPG_HIP_COLSTATS_CHUNK_ROWS: frames a lane of mlpg_hip_column_stats holds in registers
+COLSTATS_BLOCK_ROWS = 512       # MLPG_HIP_COLSTATS_BLOCK_ROWS: frames of one utterance per workgroup
+
+
+def column_stats_workspace(B, Tmax, D):
+    """mlpg_hip_column_stats_workspace: the bytes of workspace a (B, Tmax, D) batch needs (host code)."""
+    n = int(lib().mlpg_hip_column_stats_workspace(int(B), int(Tmax), int(D)))
+    if n < 0:
+        raise ValueError("column_stats: a (%d, %d, %d) batch is too large for one call" % (B, Tmax, D))
+    return n
+
+
+def column_stats(x, lengths=None, state_in=None, state_out=None, workspace=None):
+    """mlpg_hip_column_stats on CUDA tensors: x (B, Tmax, D) float32 / float64 whose last dimension is contiguous and whose first
+    two are those of a dense (B, Tmax, ld) array (a column slice of one is fine); lengths int32 (B) or None; state_in float64
+    (5, D) -- rows count, mean, M2, min, max -- or None (empty); state_out the same (None: a new tensor; state_in itself: in
+    place); workspace: a uint8 / float64 tensor of at least column_stats_workspace(B, Tmax, D) bytes (None: allocated).  Returns
+    state_out.  Two launches on the current stream, no synchronisation."""
+    torch = torch_mod()
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 3):
+        raise ValueError("column_stats: x must be a (B, Tmax, D) CUDA tensor")
+    B, T, D = x.shape
+    dev = x.device
+    _check_lengths(lengths, B, dev)
+    ld = _pf_row_stride(x, B, T, D, "column_stats")
+    for name, t in (("state_in", state_in), ("state_out", state_out)):
+        if t is not None and not (torch.is_tensor(t) and t.device == dev and t.dtype == torch.float64 and tuple(t.shape) == (5, D)
+                                  and t.is_contiguous()):
+            raise ValueError("column_stats: %s must be a contiguous float64 (5, %d) tensor on %s" % (name, D, dev))
+    if state_out is None:
+        state_out = torch.empty((5, D), dtype=torch.float64, device=dev)
+    need = column_stats_workspace(B, T, D)
+    if workspace is None:
+        workspace = torch.empty((need // 8,), dtype=torch.float64, device=dev)
+    have = workspace.numel() * workspace.element_size()
+    rc = lib().mlpg_hip_column_stats(dev.index, _stream(dev), _dt(x), _p(x), ld, _p(lengths), B, T, D, _p(state_in), _p(state_out),
+                                     _p(workspace), have)
+    _check(rc, "mlpg_hip_column_stats")
+    return state_out
+
+
+def column_affine(x, a, c, mode, lengths=None, out=None, out_dtype=None):
+    """mlpg_hip_column_affine on CUDA tensors: mode 0  (x - c) / a,  mode 1  a x + c  per column, float64 arithmetic.  x
+    (B, Tmax, D) float32 / float64, a column slice of a dense (B, Tmax, ld) tensor or dense itself; a, c float64 (D) on the
+    device; out like x in shape, float32 / float64 (None: a new dense tensor of out_dtype, default x's; x itself: in place).
+    Rows past an utterance's length come out as zeros.  One launch on the current stream."""
+    torch = torch_mod()
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 3):
+        raise ValueError("column_affine: x must be a (B, Tmax, D) CUDA tensor")
+    B, T, D = x.shape
+    dev = x.device
+    if out is None:
+        out = torch.empty((B, T, D), dtype=out_dtype or x.dtype, device=dev)
+    if not (torch.is_tensor(out) and out.device == dev and out.shape == x.shape):
+        raise ValueError("column_affine: out must have x's shape and device")
+    for name, t in (("a", a), ("c", c)):
+        if not (torch.is_tensor(t) and t.device == dev and t.dtype == torch.float64 and tuple(t.shape) == (D,) and t.is_contiguous()):
+            raise ValueError("column_affine: %s must be a contiguous float64 (%d,) tensor on %s" % (name, D, dev))
+    _check_lengths(lengths, B, dev)
+    ld_x, ld_y = _pf_row_stride(x, B, T, D, "column_affine"), _pf_row_stride(out, B, T, D, "column_affine")
+    rc = lib().mlpg_hip_column_affine(dev.index, _stream(dev), _dt(x), _dt(out), int(mode), _p(x), ld_x, _p(out), ld_y, _p(lengths),
+                                      B, T, D, _p(a), _p(c))
+    _check(rc, "mlpg_hip_column_affine")
     return out
 
 

@@ -9,7 +9,7 @@ Two situations:
 
 * the reference package is importable: the hot-path callables are replaced IN PLACE on its modules
   (``nnmnkwii.paramgen.mlpg`` and friends, the autograd functions, the aligners, ``baseline.gmm.MLPG``,
-  ``delta_features`` / ``trim_zeros_frames`` / the modspec functions, ``postfilters.merlin_post_filter``,
+  ``delta_features`` / ``trim_zeros_frames`` / the modspec functions, ``meanvar`` / ``meanstd`` / ``minmax`` and the scalers, ``postfilters.merlin_post_filter``,
   ``util.apply_each2d_*``);
   everything else of the reference (datasets, frontend, IO ...) keeps working as before;
 * it is not: lightweight ``nnmnkwii`` / ``nnmnkwii.<sub>`` module objects are registered in
@@ -31,6 +31,8 @@ from .preprocessing import alignment as _alignment
 
 _modspec = importlib.import_module(__package__ + ".preprocessing.modspec")   # the attribute of that name is the function
 
+# corpus normalisation (preprocessing/generic.py:496-829 of the reference)
+_NORM = ("meanvar", "meanstd", "minmax", "scale", "inv_scale", "minmax_scale_params", "minmax_scale", "inv_minmax_scale")
 # reference module -> {attribute: replacement}
 _SURFACE = {
     "nnmnkwii.paramgen": {k: getattr(_paramgen, k) for k in (
@@ -38,7 +40,8 @@ _SURFACE = {
     "nnmnkwii.autograd": {k: getattr(_autograd, k) for k in (
         "mlpg", "MLPG", "unit_variance_mlpg", "UnitVarianceMLPG", "modspec", "ModSpec")},
     "nnmnkwii.preprocessing": {k: getattr(_preprocessing, k) for k in (
-        "delta_features", "trim_zeros_frames", "modspec", "modphase", "inv_modspec", "modspec_smoothing")},
+        "delta_features", "trim_zeros_frames", "modspec", "modphase", "inv_modspec", "modspec_smoothing") + _NORM},
+    "nnmnkwii.preprocessing.generic": {k: getattr(_preprocessing, k) for k in ("delta_features", "trim_zeros_frames") + _NORM},
     "nnmnkwii.preprocessing.alignment": {k: getattr(_alignment, k) for k in ("DTWAligner", "IterativeDTWAligner")},
     "nnmnkwii.preprocessing.modspec": {k: getattr(_modspec, k) for k in (
         "modspec", "modphase", "inv_modspec", "modspec_smoothing")},

@@ -325,7 +325,7 @@ __attribute__((visibility("default"))) int mlpg_hip_abi_version(void) { return 1
 
 __attribute__((visibility("default"))) long long mlpg_hip_launch_count(int kind) {
   if (kind >= 100) return host_chunks_on_device(kind - 100);  // chunks the host-memory calls enqueued on device kind - 100
-  return kind >= 0 && kind < kCountKinds && kind != kCountUnused12 && kind != kCountUnused14 && kind != kCountUnused16 && kind != kCountUnused21 && kind != kCountUnused25 && kind != kCountUnused28 && kind != kCountUnused30 && kind != kCountUnused32 && kind != kCountUnused34 && kind != kCountUnused36 ? g_launches[kind].load() : -1;
+  return kind >= 0 && kind < kCountKinds && kind != kCountUnused12 && kind != kCountUnused14 && kind != kCountUnused16 && kind != kCountUnused21 && kind != kCountUnused25 && kind != kCountUnused28 && kind != kCountUnused30 && kind != kCountUnused32 && kind != kCountUnused34 && kind != kCountUnused36 && kind != kCountUnused38 && kind != kCountUnused40 ? g_launches[kind].load() : -1;
 }
 
 __attribute__((visibility("default"))) const char *mlpg_hip_last_error(void) { return g_err; }

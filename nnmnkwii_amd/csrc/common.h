@@ -140,8 +140,9 @@ SideStreams *side_streams(int device);
 // _lloyd_step that launched their kernels (kmeans.hip); 28 counts nothing and reads -1; 29: calls of mlpg_hip_merlin_post_filter that
 // launched (postfilter.hip); 30 counts nothing and reads -1; 31: launches of the kernel of mlpg_hip_modspec_filter (modspec_filter.hip); 32 counts nothing and reads -1; 33: launches of the
 // kernel of mlpg_hip_gmm_trajectory_stats (gmm_traj.hip); 34 and 36 count nothing and read -1; 35: launches of the kernel of
-// mlpg_hip_gv_ascent, 37: of mlpg_hip_gv (mlpg_gv.hip))
-enum { kCountGeneric = 0, kCountWave, kCountStrip, kCountStripMulti, kCountConst, kCountFused, kCountChunk, kCountFir, kCountConstMulti, kCountStripTr, kCountHostSmall, kCountHostSmallDirect, kCountUnused12, kCountVarGrad, kCountUnused14, kCountStreamsBwd, kCountUnused16, kCountModspecBatch, kCountModspecBatchDft, kCountModspecLoss, kCountModspecChirp, kCountUnused21, kCountGmmEstep, kCountGmmMstep, kCountGmmPrecisions, kCountUnused25, kCountKmeansSeed, kCountKmeansLloyd, kCountUnused28, kCountPostfilter, kCountUnused30, kCountModspecFilter, kCountUnused32, kCountGmmTraj, kCountUnused34, kCountGvAscent, kCountUnused36, kCountGv, kCountKinds };
+// mlpg_hip_gv_ascent, 37: of mlpg_hip_gv (mlpg_gv.hip); 38 and 40 count nothing and read -1; 39: calls of mlpg_hip_column_stats that
+// launched, 41: of mlpg_hip_column_affine (colstats.hip))
+enum { kCountGeneric = 0, kCountWave, kCountStrip, kCountStripMulti, kCountConst, kCountFused, kCountChunk, kCountFir, kCountConstMulti, kCountStripTr, kCountHostSmall, kCountHostSmallDirect, kCountUnused12, kCountVarGrad, kCountUnused14, kCountStreamsBwd, kCountUnused16, kCountModspecBatch, kCountModspecBatchDft, kCountModspecLoss, kCountModspecChirp, kCountUnused21, kCountGmmEstep, kCountGmmMstep, kCountGmmPrecisions, kCountUnused25, kCountKmeansSeed, kCountKmeansLloyd, kCountUnused28, kCountPostfilter, kCountUnused30, kCountModspecFilter, kCountUnused32, kCountGmmTraj, kCountUnused34, kCountGvAscent, kCountUnused36, kCountGv, kCountUnused38, kCountColStats, kCountUnused40, kCountColAffine, kCountKinds };
 void note_launch(int kind);
 // Grow-only scratch, cached per (device, stream, slot): slot 0 generic factor, 1 fastdtw pyramids,
 // 2 generic status, 3 strip records, 4 constant-coefficient kernel (factor table), 5 fastdtw from host costs (D rows, back-pointers), 6 chunked kernel (records, block factors, separator solutions, marks).  Returns nullptr (and sets the error) on failure.
@@ -260,6 +261,12 @@ int launch_postfilter(hipStream_t s, int dtype, const void *mgc, long ld_in, con
 int launch_gmm_traj(hipStream_t s, const double *x, long ld_x, const int32_t *lengths, int B, int Tmax, int D, const int32_t *labels,
                     const double *mu_x, const double *mu_y, const double *A, const double *cvar, int M, double *mean, long ld_mean,
                     double *var, long ld_var);
+// colstats.hip: column statistics of a padded batch (the statistics kernel and its finish step; kind kCountColStats) and the
+// per-column affine map (one launch, kind kCountColAffine)
+int launch_colstats(hipStream_t s, int dtype, const void *x, long ld_x, const int32_t *lengths, int B, int Tmax, int D,
+                    const double *state_in, double *state_out, double *workspace);
+int launch_colaffine(hipStream_t s, int in_dtype, int out_dtype, int mode, const void *x, long ld_x, void *y, long ld_y,
+                     const int32_t *lengths, int B, int Tmax, int D, const double *a, const double *c);
 int launch_gather(hipStream_t s, int dtype, const void *src, const int32_t *path, const int32_t *path_len, int N,
                   int Tsrc, int path_stride, int D, int Tout, void *out);
 

@@ -4,7 +4,8 @@ Mirrors ``apply_each2d_trim`` / ``apply_each2d_padded`` of /root/reference/nnmnk
 apply a ``(T, D) -> (T', D')`` function to every utterance of a zero-padded ``(N, Tmax, D)`` array and
 collect the results in a zero-padded ``(N, Tmax, D')`` float64 array.  When the function is one of this
 package's batched operations (``paramgen.mlpg``, ``preprocessing.delta_features``,
-``postfilters.merlin_post_filter``, ``postfilters.modspec_post_filter``, ``preprocessing.modspec_smoothing``) the whole batch goes
+``postfilters.merlin_post_filter``, ``postfilters.modspec_post_filter``, ``preprocessing.modspec_smoothing``,
+``preprocessing.scale`` / ``inv_scale`` / ``minmax_scale`` / ``inv_minmax_scale``) the whole batch goes
 to the GPU in one call instead of N; any other callable is applied per utterance, as in the reference.
 """
 import inspect
@@ -34,6 +35,8 @@ def _batched(func2d, X, lengths, args, kwargs):
         if X.shape[1] > int(kw["n"]):
             return None                  # utterances may still fit; the per-utterance path raises where one does not
         return batch(X, lengths=lengths, **kw)
+    if func2d in (_gen.scale, _gen.inv_scale, _gen.minmax_scale, _gen.inv_minmax_scale) and not {"lengths", "out"} & set(kwargs):
+        return func2d(X, *args, lengths=lengths, **kwargs)          # one mlpg_hip_column_affine launch
     if kwargs:
         return None
     if func2d is _pg.mlpg and len(args) == 2:

@@ -45,6 +45,10 @@
         against the same iteration composed from torch operations on resident tensors (banded product by shifted slices),
         alternating; medians with [min, max], the ratio and the agreement of the two routes; also written to
         profiles/gvmlpg.json (NNMNKWII_GVMLPG_PROFILE names another file)
+  norm : (only with --only norm) corpus normalisation over a padded 512 x 2000 x 187 batch, lengths in [1000, 2000], float32 and
+        float64: one mlpg_hip_column_stats call against the same five statistics composed from masked torch reductions, and
+        mlpg_hip_column_affine (scale, inv_scale) against the broadcast torch expression plus masking; milliseconds and the
+        fraction of 8 TB/s; also written to profiles/norm.json (NNMNKWII_NORM_PROFILE names another file)
 
 Each line carries the GPU time (HIP events on the launch stream), the algorithmic bytes, GB/s, and a
 bounded CPU baseline from the oracle on the same host (the checker, timed like bench.py's cpu_baseline).
@@ -1104,6 +1108,63 @@ def _run(only, quick, device_index):
         emit(**res)
         if not args.quick:
             out_path = os.environ.get("NNMNKWII_GVMLPG_PROFILE") or os.path.join(ROOT, "profiles", "gvmlpg.json")
+            with open(out_path, "w") as fh:
+                json.dump(res, fh, indent=1, sort_keys=True)
+                fh.write("\n")
+
+    # ---- norm: corpus normalisation over a config-5 sized padded batch: statistics in one pass, the affine map; only with --only norm ----
+    if args.only and "norm" in args.only.split(","):
+        B, T, D = (64, 500, 187) if args.quick else (512, 2000, 187)
+        rng = np.random.RandomState(1234)
+        lens = rng.randint(T // 2, T + 1, size=B).astype(np.int32)
+        live = int(lens.sum())
+        lengths = torch.from_numpy(lens).to(dev)
+        mask = (torch.arange(T, device=dev)[None, :] < lengths[:, None])[:, :, None]
+        res = dict(path="norm-config5", B=B, T=T, D=D, live_frames=live, hbm_peak_gbs=HBM_PEAK_GBS,
+                   chunk_rows=_hip.COLSTATS_CHUNK_ROWS, block_rows=_hip.COLSTATS_BLOCK_ROWS)
+        host = rng.randn(B, T, D) * (0.2 + rng.rand(D)) + 3.0 * rng.randn(D)
+        ws = torch.empty(_hip.column_stats_workspace(B, T, D) // 8, dtype=torch.float64, device=dev)
+        state = torch.empty((5, D), dtype=torch.float64, device=dev)
+        n = float(live)
+        inf = float("inf")
+
+        def composed_stats(x):
+            xd = x.to(torch.float64)
+            mean = (xd * mask).sum(dim=(0, 1)) / n
+            var = (((xd - mean) * mask) ** 2).sum(dim=(0, 1)) / n
+            return mean, var, torch.where(mask, xd, inf).amin(dim=(0, 1)), torch.where(mask, xd, -inf).amax(dim=(0, 1))
+
+        for name, tdt, size in (("float32", torch.float32, 4), ("float64", torch.float64, 8)):
+            x = torch.from_numpy(host).to(dev).to(tdt)
+            nbytes = float(size) * live * D
+            r = dict(stats_bytes=nbytes, apply_bytes=2 * nbytes)
+            r["stats_ms"] = gpu_time(lambda: _hip.column_stats(x, lengths, None, state, ws), steps=20)
+            r["stats_composed_ms"] = gpu_time(lambda: composed_stats(x), steps=10)
+            mean, var, mn, mx = composed_stats(x)
+            st = state.clone()
+            std = (st[2] / st[0]).sqrt()
+            r["stats_hbm_frac"] = nbytes / (r["stats_ms"] * 1e6) / HBM_PEAK_GBS
+            r["stats_mean_rel_err_vs_composed"] = float(((st[1] - mean).abs() / mean.abs()).max())
+            r["stats_var_rel_err_vs_composed"] = float(((st[2] / st[0] - var).abs() / var).max())
+            r["stats_extrema_equal"] = bool(torch.equal(st[3], mn) and torch.equal(st[4], mx))
+            out = torch.empty_like(x)
+            a, c = std.contiguous(), st[1].contiguous()
+            for mode, word, expr in ((0, "scale", lambda: torch.where(mask, (x - c) / a, 0.0).to(tdt)),
+                                     (1, "inv_scale", lambda: torch.where(mask, a * x + c, 0.0).to(tdt))):
+                r["%s_ms" % word] = gpu_time(lambda: _hip.column_affine(x, a, c, mode, lengths, out), steps=20)
+                r["%s_composed_ms" % word] = gpu_time(expr, steps=10)
+                r["%s_hbm_frac" % word] = 2 * nbytes / (r["%s_ms" % word] * 1e6) / HBM_PEAK_GBS
+                r["%s_max_abs_diff_vs_composed" % word] = float((out.to(torch.float64) - expr().to(torch.float64)).abs().max())
+            res[name] = r
+        res["note"] = ("lengths in [T/2, T]; HIP-event medians on settled clocks.  stats: ONE call of mlpg_hip_column_stats (the statistics "
+                       "kernel and its finish step, workspace given) against count, mean, variance, min and max composed from masked torch "
+                       "reductions in float64; scale / inv_scale: one launch of mlpg_hip_column_affine (modes 0 and 1) against the broadcast "
+                       "torch expression plus masking.  hbm_frac: 4 | 8 bytes * live frames * D (twice that for the apply) over the time, as "
+                       "a fraction of 8 TB/s.  The composed routes are the yardstick: the parent has no such capability.  No counters "
+                       "were collected; no time is asserted anywhere")
+        emit(**res)
+        if not args.quick:
+            out_path = os.environ.get("NNMNKWII_NORM_PROFILE") or os.path.join(ROOT, "profiles", "norm.json")
             with open(out_path, "w") as fh:
                 json.dump(res, fh, indent=1, sort_keys=True)
                 fh.write("\n")
