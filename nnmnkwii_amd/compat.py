@@ -9,7 +9,7 @@ Two situations:
 
 * the reference package is importable: the hot-path callables are replaced IN PLACE on its modules
   (``nnmnkwii.paramgen.mlpg`` and friends, the autograd functions, the aligners, ``baseline.gmm.MLPG``,
-  ``delta_features`` / ``trim_zeros_frames`` / the modspec functions, ``meanvar`` / ``meanstd`` / ``minmax`` and the scalers, ``postfilters.merlin_post_filter``,
+  ``delta_features`` / ``trim_zeros_frames`` / the modspec functions, ``meanvar`` / ``meanstd`` / ``minmax`` and the scalers, ``postfilters.merlin_post_filter``, the four functions of ``metrics``,
   ``util.apply_each2d_*``);
   everything else of the reference (datasets, frontend, IO ...) keeps working as before;
 * it is not: lightweight ``nnmnkwii`` / ``nnmnkwii.<sub>`` module objects are registered in
@@ -22,6 +22,7 @@ import sys
 import types
 
 from . import autograd as _autograd
+from . import metrics as _metrics
 from . import paramgen as _paramgen
 from . import postfilters as _postfilters
 from . import preprocessing as _preprocessing
@@ -47,6 +48,7 @@ _SURFACE = {
         "modspec", "modphase", "inv_modspec", "modspec_smoothing")},
     "nnmnkwii.baseline.gmm": {k: getattr(_gmm, k) for k in ("MLPGBase", "MLPG")},
     "nnmnkwii.postfilters": {"merlin_post_filter": _postfilters.merlin_post_filter},
+    "nnmnkwii.metrics": {k: getattr(_metrics, k) for k in ("melcd", "mean_squared_error", "lf0_mean_squared_error", "vuv_error")},
     "nnmnkwii.util": {"apply_each2d_padded": _util.apply_each2d_padded, "apply_each2d_trim": _util.apply_each2d_trim,
                       "trim_zeros_frames": _preprocessing.trim_zeros_frames,
                       "delta_features": _preprocessing.delta_features,

@@ -49,12 +49,17 @@
         float64: one mlpg_hip_column_stats call against the same five statistics composed from masked torch reductions, and
         mlpg_hip_column_affine (scale, inv_scale) against the broadcast torch expression plus masking; milliseconds and the
         fraction of 8 TB/s; also written to profiles/norm.json (NNMNKWII_NORM_PROFILE names another file)
+  metrics : (only with --only metrics) the four-term Merlin evaluation (mgc MCD, bap distortion, lf0 RMSE, V/UV error) over a padded
+        512 x 2000 x 187 float32 prediction / target pair, lengths in [1000, 2000]: one nnmk_metrics_batch call against the
+        reference's per-utterance loop and against masked vectorised torch expressions on the same tensors; milliseconds and the
+        fraction of 8 TB/s; also written to profiles/metrics.json (NNMNKWII_METRICS_PROFILE names another file)
 
 Each line carries the GPU time (HIP events on the launch stream), the algorithmic bytes, GB/s, and a
 bounded CPU baseline from the oracle on the same host (the checker, timed like bench.py's cpu_baseline).
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -1165,6 +1170,89 @@ def _run(only, quick, device_index):
         emit(**res)
         if not args.quick:
             out_path = os.environ.get("NNMNKWII_NORM_PROFILE") or os.path.join(ROOT, "profiles", "norm.json")
+            with open(out_path, "w") as fh:
+                json.dump(res, fh, indent=1, sort_keys=True)
+                fh.write("\n")
+
+    # ---- metrics: the four-term Merlin evaluation over a config-5 sized padded batch, one call; only with --only metrics ----
+    if args.only and "metrics" in args.only.split(","):
+        from nnmnkwii_amd import _metrics_hip as MH
+        from nnmnkwii_amd import metrics as MT
+        B, T, D = (64, 500, 187) if args.quick else (512, 2000, 187)
+        rng = np.random.RandomState(1234)
+        lens = rng.randint(T // 2, T + 1, size=B).astype(np.int32)
+        live = int(lens.sum())
+        lengths = torch.from_numpy(lens).to(dev)
+        # Merlin's acoustic feature matrix: mgc 0 .. 59 (MCD without the energy), lf0 60, vuv 61, bap 62 .. 64
+        MGC, LF0, VUV, BAP = slice(1, 60), 60, 61, slice(62, 65)
+        host_y = rng.randn(B, T, D).astype(np.float32)
+        host_y[:, :, LF0] = 5.0 + 0.3 * rng.randn(B, T)
+        host_y[:, :, VUV] = rng.rand(B, T) < 0.7
+        host_x = host_y + 0.3 * rng.randn(B, T, D).astype(np.float32)
+        host_x[:, :, VUV] = np.where(rng.rand(B, T) < 0.9, host_y[:, :, VUV], 1.0 - host_y[:, :, VUV])
+        X, Y = torch.from_numpy(host_x).to(dev), torch.from_numpy(host_y).to(dev)
+        terms = [MH.term(MH.FRAME_L2, 1, width=59), MH.term(MH.SQUARED, 62, width=3), MH.term(MH.VOICED_SQUARED, LF0, x_mask_col=VUV),
+                 MH.term(MH.MISMATCH, VUV)]
+        ws = torch.empty(MH.metrics_workspace(B, T, len(terms)) // 8, dtype=torch.float64, device=dev)
+        spec = {"mcd": ("melcd", MGC), "bap": ("mse", BAP), "lf0": ("lf0_mse", LF0, VUV), "vuv": ("vuv_error", VUV)}
+        lens_list = [int(n) for n in lens]
+
+        def loop():            # the reference's batched forms: a Python loop over the utterances, a float() each (metrics/__init__.py:64-183)
+            s = [0.0, 0.0, 0.0, 0.0]
+            voiced = 0
+            for x, y, n in zip(X, Y, lens_list):
+                x, y = x[:n], y[:n]
+                z = x[:, MGC] - y[:, MGC]
+                s[0] += float((z * z).sum(-1).sqrt().sum())
+                z = x[:, BAP] - y[:, BAP]
+                s[1] += float((z * z).sum())
+                v = (x[:, VUV] + y[:, VUV]) >= 2
+                voiced += int(v.sum())
+                z = x[:, LF0][v] - y[:, LF0][v]
+                s[2] += float((z * z).sum())
+                s[3] += float((x[:, VUV] != y[:, VUV]).sum())
+            return dict(mcd=float(MT._logdb_const) * s[0] / live, bap=math.sqrt(s[1] / (live * 3)), lf0=math.sqrt(s[2] / voiced), vuv=s[3] / live)
+
+        mask = torch.arange(T, device=dev)[None, :] < lengths[:, None]
+
+        def vectorised():      # masked torch expressions over the whole batch, float64 sums, one copy back
+            z = X[:, :, MGC] - Y[:, :, MGC]
+            mcd = ((z * z).sum(-1, dtype=torch.float64).sqrt() * mask).sum()
+            z = X[:, :, BAP] - Y[:, :, BAP]
+            bap = ((z * z).sum(-1, dtype=torch.float64) * mask).sum()
+            v = ((X[:, :, VUV] + Y[:, :, VUV]) >= 2) & mask
+            z = (X[:, :, LF0] - Y[:, :, LF0]).to(torch.float64)
+            lf0 = (z * z * v).sum()
+            vuv = ((X[:, :, VUV] != Y[:, :, VUV]) & mask).sum()
+            r = torch.stack([mcd, bap, lf0, v.sum().to(torch.float64), vuv.to(torch.float64)]).cpu().numpy()
+            return dict(mcd=float(MT._logdb_const) * r[0] / live, bap=math.sqrt(r[1] / (live * 3)), lf0=math.sqrt(r[2] / r[3]), vuv=r[4] / live)
+
+        nbytes = 4.0 * live * 2 * (59 + 3 + 1 + 1)             # the bytes the four terms need: 64 float32 columns of x and of y
+        span_bytes = 4.0 * live * 2 * 64                        # the bytes the kernel loads: columns 1 .. 64, the span of the terms
+        res = dict(path="metrics-config5", B=B, T=T, D=D, live_frames=live, hbm_peak_gbs=HBM_PEAK_GBS, block_rows=MH.BLOCK_ROWS,
+                   needed_bytes=nbytes, span_bytes=span_bytes)
+        res["kernel_ms"] = gpu_time(lambda: MH.metrics_batch(X, Y, terms, lengths, workspace=ws), steps=20)
+        res["kernel_hbm_frac"] = nbytes / (res["kernel_ms"] * 1e6) / HBM_PEAK_GBS
+        # the routes a user sees: wall clock to the floats on the host, everything included
+        res["one_call_wall_ms"] = wall_time(lambda: MT.batch_metrics(X, Y, lengths, spec), steps=50, warmup=5)
+        res["vectorised_wall_ms"] = wall_time(vectorised, steps=20, warmup=3)
+        res["loop_wall_ms"] = wall_time(loop, steps=2, warmup=1, repeats=2)
+        res["vectorised_over_one_call"] = res["vectorised_wall_ms"] / res["one_call_wall_ms"]
+        res["loop_over_one_call"] = res["loop_wall_ms"] / res["one_call_wall_ms"]
+        a, b, c = MT.batch_metrics(X, Y, lengths, spec), vectorised(), loop()
+        res["values"] = a
+        res["max_rel_diff_vs_vectorised"] = max(abs(a[k] - b[k]) / abs(b[k]) for k in a)
+        res["max_rel_diff_vs_loop"] = max(abs(a[k] - c[k]) / abs(c[k]) for k in a)
+        res["note"] = ("float32 (B, T, 187) prediction and target, lengths in [T/2, T]; terms: mgc MCD (59 columns), bap distortion (3), lf0 "
+                       "RMSE on voiced frames, V/UV error.  kernel_ms: HIP-event median of ONE call of nnmk_metrics_batch (both launches, "
+                       "workspace given) on settled clocks; kernel_hbm_frac: the bytes the terms need over that time as a fraction of 8 TB/s.  "
+                       "*_wall_ms: wall clock of a whole evaluation down to Python floats -- batch_metrics (the kernel, one copy of 8 doubles), "
+                       "masked vectorised torch expressions with float64 sums (one copy), and the reference's per-utterance loop with a "
+                       "float() per reduction (float32 sums, as the reference) -- all on the same tensors.  No counters were collected; no "
+                       "time is asserted anywhere")
+        emit(**res)
+        if not args.quick:
+            out_path = os.environ.get("NNMNKWII_METRICS_PROFILE") or os.path.join(ROOT, "profiles", "metrics.json")
             with open(out_path, "w") as fh:
                 json.dump(res, fh, indent=1, sort_keys=True)
                 fh.write("\n")
