@@ -181,34 +181,45 @@ __global__ __launch_bounds__(256) void colstats_finish_kernel(const double *__re
 }
 
 constexpr int kCaRows = 64;   // rows per workgroup of the apply kernel: wave w takes rows w, w + 4, ...
+// The grid of a launch is 32 bits of THREADS: with 256 threads per workgroup at most 2^24 - 1 workgroups.  A launch asked for more
+// runs (blocks * 256) mod 2^32 threads and reports nothing -- 2^31 + 32768 rows came back with the first 32768 done.  Beyond this
+// many row blocks the workgroups walk the blocks with the grid as their stride.
+constexpr long kCaMaxBlocks = (1L << 24) - 1;
+constexpr long kCsMaxBlocks = (1L << 24) - 1;  // the statistics kernel takes one workgroup per partial and column group: more are refused
 
 // One row at a time per wave, the lanes over its columns.  Measured against two forms that keep eight rows of a column in
 // flight per lane: this one is the fastest of the three.
 template <typename TX, typename TY>
 __global__ __launch_bounds__(256) void colaffine_kernel(const TX *x, long ld_x, TY *y, long ld_y, const int32_t *__restrict__ lengths,
-                                                        long rows, int Tmax, int D, int mode, const double *__restrict__ a,
-                                                        const double *__restrict__ c) {
+                                                        long rows, long stride, int Tmax, int D, int mode,
+                                                        const double *__restrict__ a, const double *__restrict__ c) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const long n0 = (long)blockIdx.x * kCaRows;
-  for (int r = wave; r < kCaRows; r += 4) {
-    const long n = n0 + r;
-    if (n >= rows) break;
-    const long b = n / Tmax;
-    const int t = (int)(n - b * Tmax);
-    int live = Tmax;
-    if (lengths) {
-      live = lengths[b];
-      live = live < 0 ? 0 : (live > Tmax ? Tmax : live);
-    }
-    TY *yr = y + (size_t)n * ld_y;
-    if (t >= live) {
-      for (int d = lane; d < D; d += 64) yr[d] = (TY)0;
-      continue;
-    }
-    const TX *xr = x + (size_t)n * ld_x;
-    for (int d = lane; d < D; d += 64) {
-      const double v = (double)xr[d];
-      yr[d] = (TY)(mode == 0 ? (v - c[d]) / a[d] : a[d] * v + c[d]);
+  const long nblk = (rows + kCaRows - 1) / kCaRows;
+  // stride: the workgroups of the launch.  An argument and not gridDim.x because this file is also compiled for the host
+  // (tests/test_norm_host_cpu.py), against a shim that defines threadIdx and blockIdx only.  One pass unless the batch has more
+  // than kCaMaxBlocks row blocks.
+  for (long blk = blockIdx.x; blk < nblk; blk += stride) {
+    const long n0 = blk * kCaRows;
+    for (int r = wave; r < kCaRows; r += 4) {
+      const long n = n0 + r;
+      if (n >= rows) break;
+      const long b = n / Tmax;
+      const int t = (int)(n - b * Tmax);
+      int live = Tmax;
+      if (lengths) {
+        live = lengths[b];
+        live = live < 0 ? 0 : (live > Tmax ? Tmax : live);
+      }
+      TY *yr = y + (size_t)n * ld_y;
+      if (t >= live) {
+        for (int d = lane; d < D; d += 64) yr[d] = (TY)0;
+        continue;
+      }
+      const TX *xr = x + (size_t)n * ld_x;
+      for (int d = lane; d < D; d += 64) {
+        const double v = (double)xr[d];
+        yr[d] = (TY)(mode == 0 ? (v - c[d]) / a[d] : a[d] * v + c[d]);
+      }
     }
   }
 }
@@ -252,15 +263,16 @@ template <typename TX>
 static void launch_colaffine_out(hipStream_t st, int out_dtype, unsigned blocks, const TX *x, long ld_x, void *y, long ld_y,
                                  const int32_t *lengths, long rows, int Tmax, int D, int mode, const double *a, const double *c) {
   if (out_dtype == MLPG_HIP_F64)
-    hipLaunchKernelGGL((colaffine_kernel<TX, double>), dim3(blocks), dim3(256), 0, st, x, ld_x, (double *)y, ld_y, lengths, rows, Tmax, D, mode, a, c);
+    hipLaunchKernelGGL((colaffine_kernel<TX, double>), dim3(blocks), dim3(256), 0, st, x, ld_x, (double *)y, ld_y, lengths, rows, (long)blocks, Tmax, D, mode, a, c);
   else
-    hipLaunchKernelGGL((colaffine_kernel<TX, float>), dim3(blocks), dim3(256), 0, st, x, ld_x, (float *)y, ld_y, lengths, rows, Tmax, D, mode, a, c);
+    hipLaunchKernelGGL((colaffine_kernel<TX, float>), dim3(blocks), dim3(256), 0, st, x, ld_x, (float *)y, ld_y, lengths, rows, (long)blocks, Tmax, D, mode, a, c);
 }
 
 int launch_colaffine(hipStream_t st, int in_dtype, int out_dtype, int mode, const void *x, long ld_x, void *y, long ld_y,
                      const int32_t *lengths, int B, int Tmax, int D, const double *a, const double *c) {
   const long rows = (long)B * Tmax;
-  const unsigned blocks = (unsigned)((rows + kCaRows - 1) / kCaRows);
+  const long nblk = (rows + kCaRows - 1) / kCaRows;
+  const unsigned blocks = (unsigned)(nblk < kCaMaxBlocks ? nblk : kCaMaxBlocks);
   if (in_dtype == MLPG_HIP_F64)
     launch_colaffine_out(st, out_dtype, blocks, (const double *)x, ld_x, y, ld_y, lengths, rows, Tmax, D, mode, a, c);
   else
@@ -304,7 +316,7 @@ __attribute__((visibility("default"))) int mlpg_hip_column_stats(int device, voi
   }
   const int64_t need = cs_workspace_bytes(B, Tmax, D);
   // (need >= 0: partials * 40 D fits 63 bits, so partials * ceil(D / 64) does)
-  if (need < 0 || cs_partials(B, Tmax) * ((D + 63) / 64) > 2147483647LL) {
+  if (need < 0 || cs_partials(B, Tmax) * ((D + 63) / 64) > kCsMaxBlocks) {
     set_error("%s: the batch is too large for one call (B = %d, Tmax = %d, D = %d)", who, B, Tmax, D);
     return MLPG_HIP_EINVAL;
   }
@@ -348,6 +360,7 @@ __attribute__((visibility("default"))) int mlpg_hip_column_affine(int device, vo
     set_error("%s: row strides must be at least D = %d (got ld_x = %lld, ld_y = %lld)", who, D, (long long)ld_x, (long long)ld_y);
     return MLPG_HIP_EINVAL;
   }
+  // (the apply kernel walks its row blocks, any number of them: what this refuses is a row count beyond 2^37)
   if (((int64_t)B * Tmax + kCaRows - 1) / kCaRows > 2147483647LL) {
     set_error("%s: the batch is too large for one call (B = %d, Tmax = %d)", who, B, Tmax);
     return MLPG_HIP_EINVAL;

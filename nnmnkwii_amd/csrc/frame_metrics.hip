@@ -347,7 +347,7 @@ __attribute__((visibility("default"))) int nnmk_metrics_batch(int device, void *
   if ((xslab + yslab) * 8 > NNMK_METRICS_MAX_ROW_BYTES)
     return mt_refuse("metrics: the terms span %lld bytes of a frame of x and y, at most %lld fit", (xslab + yslab) * 8, NNMK_METRICS_MAX_ROW_BYTES);
   const int64_t need = mt_workspace_bytes(B, Tmax, nterms);
-  if (need < 0 || (int64_t)B * mt_blocks(Tmax) > 2147483647LL)
+  if (need < 0 || (int64_t)B * mt_blocks(Tmax) > 16777215LL /* 2^24 - 1 workgroups of 256 threads: a grid is 32 bits of threads, a larger one runs truncated and reports nothing */)
     return mt_refuse("metrics: the batch is too large for one grid (B = %lld, Tmax = %lld)", B, Tmax);
   if (int rc = check_device(who, device)) return rc;
   if (!totals) return mt_refuse("metrics: NULL totals");

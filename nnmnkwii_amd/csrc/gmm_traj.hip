@@ -181,7 +181,7 @@ __attribute__((visibility("default"))) int mlpg_hip_gmm_trajectory_stats(int dev
     set_error("%s: the number of mixtures must be in [1, %d] (got %d)", who, kTrajMaxM, M);
     return MLPG_HIP_EINVAL;
   }
-  if (B < 0 || Tmax < 0 || ((int64_t)B * Tmax + kTrajRows - 1) / kTrajRows > 2147483647LL) {
+  if (B < 0 || Tmax < 0 || ((int64_t)B * Tmax + kTrajRows - 1) / kTrajRows > 16777215LL /* 2^24 - 1 workgroups of 256 threads: a grid is 32 bits of threads, a larger one runs truncated and reports nothing */) {
     set_error("%s: bad batch shape (B = %d, Tmax = %d)", who, B, Tmax);
     return MLPG_HIP_EINVAL;
   }

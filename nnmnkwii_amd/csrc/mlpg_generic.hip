@@ -298,7 +298,7 @@ int launch_stream_copy(hipStream_t st, const void *src, void *dst, size_t nbytes
   const size_t n16 = nbytes / 16;
   if (n16 == 0) return 0;
   const size_t blocks = (n16 + 255) / 256;
-  if (blocks > 0x7fffffffull) {
+  if (blocks > 16777215ull /* 2^24 - 1 workgroups of 256 threads: a grid is 32 bits of threads, a larger one runs truncated and reports nothing */) {
     set_error("stream_copy: buffer too large");
     return MLPG_HIP_EINVAL;
   }

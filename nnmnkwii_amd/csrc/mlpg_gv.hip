@@ -283,7 +283,7 @@ __attribute__((visibility("default"))) int mlpg_hip_gv_ascent(int device, void *
                                                               const double *gv_mean, const double *gv_prec, double omega_scale,
                                                               int n_iter, double step, int init, double *report, int32_t *status) {
   const char *who = "gv_ascent";
-  if (B < 0 || Tmax < 0 || D < 0 || (int64_t)B * D > 2147483647LL) {
+  if (B < 0 || Tmax < 0 || D < 0 || (int64_t)B * D > 67108863LL /* 2^26 - 1 workgroups of 64 threads (D >= sd): a grid is 32 bits of threads */) {
     set_error("%s: bad batch shape (B = %d, Tmax = %d, D = %d)", who, B, Tmax, D);
     return MLPG_HIP_EINVAL;
   }
@@ -337,7 +337,7 @@ __attribute__((visibility("default"))) int mlpg_hip_gv_ascent(int device, void *
 __attribute__((visibility("default"))) int mlpg_hip_gv(int device, void *stream, int dtype, const void *x, int64_t ld_x,
                                                        const int32_t *lengths, int B, int Tmax, int D, double *out) {
   const char *who = "gv";
-  if (B < 0 || Tmax < 0 || D < 0 || (int64_t)B * D > 2147483647LL * 256) {
+  if (B < 0 || Tmax < 0 || D < 0 || (int64_t)B * D > 16777215LL * 256 /* 2^24 - 1 workgroups of 256 threads: a grid is 32 bits of threads, a larger one runs truncated and reports nothing */) {
     set_error("%s: bad batch shape (B = %d, Tmax = %d, D = %d)", who, B, Tmax, D);
     return MLPG_HIP_EINVAL;
   }

@@ -76,7 +76,7 @@ void launch_t(hipStream_t st, unsigned grid, const void *grad_out, const void *v
 }  // namespace
 
 bool streams_bwd_fits(int B, int Tmax, int total) {
-  return ((long)B * Tmax * total + 255) / 256 <= 0x7fffffffL;
+  return ((long)B * Tmax * total + 255) / 256 <= 16777215L;  // 2^24 - 1 workgroups of 256 threads: a grid is 32 bits of threads, a larger one runs truncated and reports nothing
 }
 
 int launch_streams_bwd(hipStream_t st, int dtype, int mode, const void *grad_out, const void *var, const void *mean,

@@ -53,7 +53,7 @@ int launch_var_grad(hipStream_t st, int dtype, const void *grad_mean, const void
   const long total = (long)B * Tmax * sd;
   if (total == 0) return 0;
   const long blocks = (total + 255) / 256;
-  if (blocks > 0x7fffffffL) {
+  if (blocks > 16777215L /* 2^24 - 1 workgroups of 256 threads: a grid is 32 bits of threads, a larger one runs truncated and reports nothing */) {
     set_error("backward_var: batch too large");
     return MLPG_HIP_EINVAL;
   }

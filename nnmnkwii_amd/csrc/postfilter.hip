@@ -217,7 +217,7 @@ __attribute__((visibility("default"))) int mlpg_hip_merlin_post_filter(int devic
   // (the order went into G: any order the table builder accepts is fine here, D - 1 always is)
   if (int rc = refuse_limits(who, D, alpha, D - 1 < fftlen ? D - 1 : 0, fftlen)) return rc;
   if (int rc = check_dtype(who, dtype)) return rc;
-  if (B < 0 || Tmax < 0 || ((int64_t)B * Tmax + kPfFrames - 1) / kPfFrames > 2147483647LL) {
+  if (B < 0 || Tmax < 0 || ((int64_t)B * Tmax + kPfFrames - 1) / kPfFrames > 16777215LL /* 2^24 - 1 workgroups of 256 threads: a grid is 32 bits of threads, a larger one runs truncated and reports nothing */) {
     set_error("%s: bad batch shape (B = %d, Tmax = %d)", who, B, Tmax);
     return MLPG_HIP_EINVAL;
   }

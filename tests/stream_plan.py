@@ -5,7 +5,9 @@ exactly; under AUTO only the merged launch and the number of launches are.
 
 A stream is a dict with in_col, out_col, static_dim, num_windows, win_first (mlpg_hip_stream_t); the window tables are the
 packed (l[], u[], coeff[]) of include/mlpg_hip.h.  The support and preference predicates below restate csrc/mlpg_*.hip for
-the problems the stream tests build (every row inside the 2 GB buffer window)."""
+the problems the stream tests build.  rows_fit_buffer is the one rule (csrc/common.h) that keeps the strip, constant-coefficient,
+chunked and FIR kernels inside the 2 GB window of their buffer descriptors: `ld` is the larger of the input's and the output's row
+stride, and the predicates that take it default to 0 (a problem that fits)."""
 import collections
 
 import numpy as np
@@ -35,12 +37,17 @@ class Win(object):
 
 # ---- support / preference predicates (csrc/mlpg_strip.hip, mlpg_wave.hip, mlpg_const.hip, mlpg_chunk.hip, mlpg_fir.hip)
 
-def strip_supported(T, ws):
-    return T >= 1 and (T + STRIP_FRAMES - 1) // STRIP_FRAMES <= MAX_STRIPS and ws.ext1
+def rows_fit_buffer(T, ld):
+    """common.h rows_fit_buffer: Tmax * row stride * 8 bytes (whatever the dtype) inside the descriptor's 2^31 - 1 bytes."""
+    return float(T) * float(ld) * 8.0 < 2147483647.0
 
 
-def strip_preferred(B, T, sd, var_mode, ws):
-    if not strip_supported(T, ws):
+def strip_supported(T, ws, ld=0):
+    return T >= 1 and (T + STRIP_FRAMES - 1) // STRIP_FRAMES <= MAX_STRIPS and ws.ext1 and rows_fit_buffer(T, ld)
+
+
+def strip_preferred(B, T, sd, var_mode, ws, ld=0):
+    if not strip_supported(T, ws, ld):
         return False
     if sd >= 16 and T > 1024:
         return True
@@ -50,7 +57,7 @@ def strip_preferred(B, T, sd, var_mode, ws):
 
 
 def strip_tr_supported(B, T, sd, ld, ws):
-    if ws.nw != 3 or sd < 1 or sd > 32 or B < 2 or not strip_supported(T, ws):
+    if ws.nw != 3 or sd < 1 or sd > 32 or B < 2 or not strip_supported(T, ws, ld):
         return False
     return (64 // sd) * T * ld * 8.0 < 2147483647.0
 
@@ -71,29 +78,29 @@ def wave_supported(T, ws):
     return 1 <= T <= 2048 and ws.ext1
 
 
-def const_supported(B, T, sd, var_mode, ws, piece=False):
+def const_supported(B, T, sd, var_mode, ws, piece=False, ld=0):
     return (var_mode in (VAR_GLOBAL, VAR_UNIT) and ws.nw in (2, 3) and ws.mw == 1 and ws.ext1 and not piece
-            and T >= 1 and sd >= 1 and B >= 1)
+            and T >= 1 and sd >= 1 and B >= 1 and rows_fit_buffer(T, ld))
 
 
-def const_preferred(B, T, sd, var_mode, ws):
-    if not const_supported(B, T, sd, var_mode, ws):
+def const_preferred(B, T, sd, var_mode, ws, ld=0):
+    if not const_supported(B, T, sd, var_mode, ws, ld=ld):
         return False
     ndg = (sd + 63) // 64
     return (sd + ndg - 1) // ndg >= 32 and B * ndg >= 192
 
 
-def chunk_supported(ws, piece=False):
-    return 1 <= ws.nw <= 3 and 1 <= ws.mw <= 2 and not piece
+def chunk_supported(ws, piece=False, T=0, ld=0):
+    return 1 <= ws.nw <= 3 and 1 <= ws.mw <= 2 and not piece and rows_fit_buffer(T, ld)
 
 
-def chunk_preferred(B, T, sd, ws):
-    return chunk_supported(ws) and ws.mw == 2 and B * sd >= 64 and T >= 64
+def chunk_preferred(B, T, sd, ws, ld=0):
+    return chunk_supported(ws, T=T, ld=ld) and ws.mw == 2 and B * sd >= 64 and T >= 64
 
 
-def fir_shape_supported(B, T, sd, dtype, var_mode, has_lengths, ws, piece=False):
+def fir_shape_supported(B, T, sd, dtype, var_mode, has_lengths, ws, piece=False, ld=0):
     return (dtype == F32 and var_mode == VAR_UNIT and not has_lengths and 1 <= ws.nw <= 3 and ws.mw <= 2 and ws.l[0] == 0
-            and ws.u[0] == 0 and ws.c0 != 0.0 and not piece and T >= 96 and B >= 1 and sd >= 1)
+            and ws.u[0] == 0 and ws.c0 != 0.0 and not piece and T >= 96 and B >= 1 and sd >= 1 and rows_fit_buffer(T, ld))
 
 
 # ---- the plan
@@ -107,6 +114,7 @@ static dims that run on their own launch (or a copy, for pass-through streams), 
 
 def merge_plan(streams, wl, wu, wc, algo, var_mode, dtype, B, T, ld_in, ld_out):
     n_str = len(streams)
+    ld = max(ld_in, ld_out)
     merge_strip = algo in (AUTO, STRIP) and var_mode == VAR_FRAME
     merge_const = algo in (AUTO, CONST) and var_mode in (VAR_GLOBAL, VAR_UNIT)
     attempted = merge_strip or merge_const
@@ -167,9 +175,9 @@ def merge_plan(streams, wl, wu, wc, algo, var_mode, dtype, B, T, ld_in, ld_out):
             ws = Win(wl, wu, wc, streams[first]["win_first"], 3)
             if merge_strip:
                 sdw = min(pos, 64)
-                ok = strip_supported(T, ws) and (algo == STRIP or strip_preferred(B, T, sdw, var_mode, ws))
+                ok = strip_supported(T, ws, ld) and (algo == STRIP or strip_preferred(B, T, sdw, var_mode, ws, ld))
             else:
-                ok = ws.mw == 1 and (algo == CONST or B * ((pos + 63) // 64) >= 192)
+                ok = ws.mw == 1 and rows_fit_buffer(T, ld) and (algo == CONST or B * ((pos + 63) // 64) >= 192)
         if not ok:
             piece, piece_first = -1, 0
     merged_set = set(members) - {piece} if ok else set()
@@ -188,13 +196,13 @@ def solo_kind(s, ws, algo, var_mode, dtype, B, T, has_lengths, ld, sd, piece):
         algo = AUTO                                   # a piece goes to the kernels that take the window pitch separately
     if algo == WAVE and not wave_supported(T, ws):
         raise Refused("MLPG_HIP_ALGO_WAVE")
-    if algo == STRIP and not strip_supported(T, ws):
+    if algo == STRIP and not strip_supported(T, ws, ld):
         raise Refused("MLPG_HIP_ALGO_STRIP")
-    if algo == CONST and not const_supported(B, T, sd, var_mode, ws):
+    if algo == CONST and not const_supported(B, T, sd, var_mode, ws, ld=ld):
         raise Refused("MLPG_HIP_ALGO_CONST")
-    if algo == CHUNK and not chunk_supported(ws):
+    if algo == CHUNK and not chunk_supported(ws, T=T, ld=ld):
         raise Refused("MLPG_HIP_ALGO_CHUNK")
-    if algo == FIR and not fir_shape_supported(B, T, sd, dtype, var_mode, has_lengths, ws):
+    if algo == FIR and not fir_shape_supported(B, T, sd, dtype, var_mode, has_lengths, ws, ld=ld):
         raise Refused("MLPG_HIP_ALGO_FIR")
     if algo == FIR:
         return K_FIR

@@ -128,6 +128,42 @@ def test_forward_streams_refuses_a_forced_family_before_any_launch(L):
         assert rc == -1 and word in err, (kw, rc, err)
 
 
+def test_forward_streams_refuses_the_windowed_families_beyond_the_2_gb_window(L):
+    """rows_fit_buffer (csrc/common.h): Tmax * row stride * 8 < 2^31 - 1 for the kernels that address an utterance through a buffer
+    descriptor.  130 * 2064888 * 8 = 2^31 - 128 is inside; with one element more per row -- on the input or on the output side,
+    in either dtype -- a forced STRIP, CONST, CHUNK or FIR is refused from the plan, before a device is selected: EINVAL, the
+    stream and the family named, no counter moved (the pointers are fakes: a call that got as far as a launch would fault).
+    tests/test_far_rows_gpu.py runs the accepted side of the rule, and AUTO beyond it."""
+    from nnmnkwii_amd._hip import StreamDesc
+    wl = np.array([0, 1, 1, 2], dtype=np.int32)
+    wu = np.array([0, 1, 1, 2], dtype=np.int32)
+    wc = np.array([1.0, -0.5, 0.0, 0.5, 1.0, -2.0, 1.0, 1.0, -8.0, 0.0, 8.0, -1.0])
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    fake = ctypes.c_void_p(64)
+    std = (StreamDesc * 1)(StreamDesc(0, 0, 40, 3, 0))                # the standard windows
+    ext2 = (StreamDesc * 1)(StreamDesc(0, 0, 10, 1, 3))               # one window of extent 2
+    assert 130 * 2064888 * 8 == 2 ** 31 - 128
+
+    def call(tab, dtype, algo, var_mode, ld_in, ld_out):
+        c0 = [L.mlpg_hip_launch_count(k) for k in range(16)]
+        rc = L.mlpg_hip_forward_streams(0, None, dtype, algo, fake, fake, var_mode, ld_in, None, 3, 130, 1, ctypes.addressof(tab), 4,
+                                        p(wl), p(wu), p(wc), fake, ld_out, None)
+        assert [L.mlpg_hip_launch_count(k) for k in range(16)] == c0
+        return rc, L.mlpg_hip_last_error().decode()
+
+    for ld_in, ld_out in ((2064889, 40), (120, 2064889)):
+        for dtype in (0, 1):
+            for tab, algo, var_mode, name in ((std, 3, 0, "STRIP"), (std, 5, 1, "CONST"), (std, 5, 2, "CONST"), (ext2, 6, 0, "CHUNK"),
+                                              (std, 7, 2, "FIR")):
+                if name == "FIR" and dtype == 1:
+                    continue                                          # (float64: refused whatever the stride)
+                rc, err = call(tab, dtype, algo, var_mode, max(ld_in, 30) if tab is ext2 else ld_in, ld_out)
+                assert rc == -1 and "stream 0: MLPG_HIP_ALGO_" + name in err, (ld_in, ld_out, dtype, name, rc, err)
+    # a row stride the int32 columns of the table cannot address is refused as a size
+    rc, err = call(std, 1, 0, 0, 2 ** 31, 40)
+    assert rc == -1 and "oversized" in err, err
+
+
 def test_unit_mse_form_validates_without_gpu(L):
     wl = np.array([0, 1], dtype=np.int32)
     wu = np.array([0, 1], dtype=np.int32)

@@ -124,3 +124,69 @@ def test_forced_family_counters_and_refusals():
         assert str(ei.value) == "MLPG_HIP_ALGO_" + SP.ALGO_NAME[algo]
     plan, kinds, n = SP.predict(mixed, wl, wu, wc, SP.GENERIC, SP.VAR_FRAME, SP.F64, 6, 300, ld, ld, True)
     assert kinds == {SP.K_GENERIC: 5} and not plan.attempted
+
+
+# ---------------------------------------------------------------------------------------------------- the 2 GB window rule
+
+def test_rows_fit_buffer_is_the_rule_of_common_h():
+    """Tmax * ld * 8 < 2^31 - 1 whatever the dtype: 130 rows of 2064888 elements are 2^31 - 128 bytes, one element more per
+    row is past the line."""
+    assert 130 * 2064888 * 8 == 2 ** 31 - 128
+    assert SP.rows_fit_buffer(130, 2064888) and not SP.rows_fit_buffer(130, 2064889)
+    assert SP.rows_fit_buffer(1, 268435455) and not SP.rows_fit_buffer(1, 268435456)      # 2^31 - 8 | 2^31 bytes
+    assert SP.rows_fit_buffer(0, 0) and SP.rows_fit_buffer(2048, 131071) and not SP.rows_fit_buffer(2048, 131072)
+
+
+def test_every_family_that_needs_the_window_is_refused_beyond_it_and_the_plan_does_not_merge():
+    spec = [(60, "std3"), (1, "std3"), (5, "std3")]
+    streams, wl, wu, wc, _ = _table(spec)
+    wide_streams, wl2, wu2, wc2, _ = _table([(24, "wide3")])
+    for ld, fits in ((2064888, True), (2064889, False)):
+        for algo, mode, dt, tab in ((SP.STRIP, SP.VAR_FRAME, SP.F64, (streams, wl, wu, wc)),
+                                    (SP.CONST, SP.VAR_GLOBAL, SP.F64, (streams, wl, wu, wc)),
+                                    (SP.CHUNK, SP.VAR_FRAME, SP.F64, (wide_streams, wl2, wu2, wc2)),
+                                    (SP.FIR, SP.VAR_UNIT, SP.F32, (streams, wl, wu, wc))):
+            for ld_in, ld_out in ((ld, 66), (200, ld)):                                   # the wide side is either one
+                if fits:
+                    plan, kinds, n = SP.predict(*tab, algo, mode, dt, 3, 130, ld_in, ld_out, False)
+                    assert plan.merged == (algo in (SP.STRIP, SP.CONST)), (algo, ld_in, ld_out)
+                else:
+                    with pytest.raises(SP.Refused) as ei:
+                        SP.predict(*tab, algo, mode, dt, 3, 130, ld_in, ld_out, False)
+                    assert str(ei.value) == "MLPG_HIP_ALGO_" + SP.ALGO_NAME[algo]
+        # the families that take any stride, and AUTO, which then has only those: no merged launch
+        for algo, kind in ((SP.WAVE, SP.K_WAVE), (SP.GENERIC, SP.K_GENERIC)):
+            plan, kinds, n = SP.predict(streams, wl, wu, wc, algo, SP.VAR_FRAME, SP.F64, 3, 130, ld, 66, False)
+            assert kinds == {kind: 3} and not plan.attempted
+        for mode, B, T in ((SP.VAR_FRAME, 1, 1100), (SP.VAR_GLOBAL, 192, 130)):
+            ld_t = ld if T == 130 else (244032 if fits else 244033)                       # 1100 * 244033 * 8 >= 2^31 - 1
+            plan, kinds, n = SP.predict(streams, wl, wu, wc, SP.AUTO, mode, SP.F64, B, T, ld_t, 66, False)
+            assert plan.attempted and plan.merged == fits and n == (2 if fits else 3), (mode, fits, plan)
+    # the transposed form has the rule for its group of u = 64 // sd utterances
+    ws = SP.Win(wl, wu, wc, 0, 3)
+    assert 12 * 130 * 172074 * 8 < 2147483647 <= 12 * 130 * 172075 * 8
+    assert SP.strip_tr_supported(24, 130, 5, 172074, ws) and not SP.strip_tr_supported(24, 130, 5, 172075, ws)
+    assert SP.strip_supported(130, ws, 172075)                                            # the plain form still takes it
+    assert SP.solo_kind(None, ws, SP.STRIP, SP.VAR_FRAME, SP.F64, 24, 130, False, 172074, 5, False) == SP.K_STRIP_TR
+    assert SP.solo_kind(None, ws, SP.STRIP, SP.VAR_FRAME, SP.F64, 24, 130, False, 172075, 5, False) == SP.K_STRIP
+
+
+def test_the_rule_changes_no_prediction_of_the_route_tests(monkeypatch):
+    """Every problem tests/test_stream_routes_gpu.py builds lies inside the window, for the transposed form's group too, and
+    is predicted as it was before the rule was restated."""
+    import test_stream_routes_gpu as R
+    cells = list(R.CELLS) + list(R.SWEEP)
+    assert len(cells) > 300
+    with_rule = []
+    for lname, dt, mode, ragged, algo, T, B, _ in cells:
+        lay = R.layout(lname)
+        ld = max(lay.ld_in, lay.ld_out)
+        assert SP.rows_fit_buffer(T, ld) and 64 * T * ld * 8.0 < 2147483647.0, (lname, T, ld)
+        with_rule.append(lay.predict(algo, mode, dt, B, T, ragged))
+    monkeypatch.setattr(SP, "rows_fit_buffer", lambda T, ld: True)
+    for cell, want in zip(cells, with_rule):
+        lname, dt, mode, ragged, algo, T, B, _ = cell
+        assert R.layout(lname).predict(algo, mode, dt, B, T, ragged) == want, cell
+    for spec in (R.LAY_SIDE,):
+        lay = R.Layout(spec, 11)
+        assert SP.rows_fit_buffer(1100, max(lay.ld_in, lay.ld_out))
