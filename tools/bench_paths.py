@@ -53,6 +53,11 @@
         512 x 2000 x 187 float32 prediction / target pair, lengths in [1000, 2000]: one nnmk_metrics_batch call against the
         reference's per-utterance loop and against masked vectorised torch expressions on the same tensors; milliseconds and the
         fraction of 8 TB/s; also written to profiles/metrics.json (NNMNKWII_METRICS_PROFILE names another file)
+  frontend : (only with --only frontend) phone-level linguistic features expanded to frames: 512 utterances of 60 .. 100 phones x 5
+        states, 1000 .. 2000 frames each, Dl = 416, kind full, float32 (512, 2000, 425) out, without and with the fused affine map:
+        one nnmk_frontend_expand launch against the same result composed from torch operations and against the specification's
+        per-frame loop on eight utterances (scaled); milliseconds and the fraction of 8 TB/s; also written to
+        profiles/frontend.json (NNMNKWII_FRONTEND_PROFILE names another file)
 
 Each line carries the GPU time (HIP events on the launch stream), the algorithmic bytes, GB/s, and a
 bounded CPU baseline from the oracle on the same host (the checker, timed like bench.py's cpu_baseline).
@@ -1253,6 +1258,94 @@ def _run(only, quick, device_index):
         emit(**res)
         if not args.quick:
             out_path = os.environ.get("NNMNKWII_METRICS_PROFILE") or os.path.join(ROOT, "profiles", "metrics.json")
+            with open(out_path, "w") as fh:
+                json.dump(res, fh, indent=1, sort_keys=True)
+                fh.write("\n")
+
+    # ---- frontend: phone-level linguistic features expanded to frames over a config-5 sized padded batch; only with --only frontend ----
+    if args.only and "frontend" in args.only.split(","):
+        from nnmnkwii_amd import _frontend_hip as FH
+        from nnmnkwii_amd.frontend import merlin as FE
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import frontend_model as FM
+        B, Tlo, Thi, Dl, S = (32, 1000, 2000, 416, 5) if args.quick else (512, 1000, 2000, 416, 5)
+        rng = np.random.RandomState(1234)
+        nph = rng.randint(60, 101, size=B).astype(np.int32)
+        Nmax, F = 100, 9
+        W = Dl + F
+        frames = rng.randint(Tlo, Thi + 1, size=B)
+        host_d = np.zeros((B, Nmax, S), dtype=np.int32)
+        for b in range(B):                                   # the utterance's frames dealt to its states
+            host_d[b, :nph[b]] = rng.multinomial(frames[b], np.ones(nph[b] * S) / (nph[b] * S)).reshape(nph[b], S)
+        host_P = ((rng.rand(B, Nmax, Dl) < 0.2) + (rng.rand(B, Nmax, Dl) < 0.05) * rng.randn(B, Nmax, Dl)).astype(np.float32)
+        scale_h, min_h = rng.rand(W) + 0.5, rng.randn(W)
+        P, d, n = torch.from_numpy(host_P).to(dev), torch.from_numpy(host_d).to(dev), torch.from_numpy(nph).to(dev)
+        sc, mn = torch.from_numpy(scale_h).to(dev), torch.from_numpy(min_h).to(dev)
+        Tmax = Thi
+        out = torch.empty((B, Tmax, W), dtype=torch.float32, device=dev)
+        live = int(frames.sum())
+        # the composed torch route, on the same tensors: the state of every frame by repeat_interleave, the nine columns by tensor
+        # arithmetic in float64, the phone rows gathered, cat, the affine expression, one rounding, the rows placed into the padded batch
+        r = d.to(torch.int64) * (torch.arange(Nmax, device=dev)[None, :, None] < n[:, None, None])
+        state_ids = torch.arange(B * Nmax * S, device=dev)
+
+        def composed(affine):
+            rf = r.reshape(-1)
+            idx = torch.repeat_interleave(state_ids, rf, output_size=live)            # the state of every frame of the batch
+            ends = torch.cumsum(rf, 0)
+            g = torch.arange(live, device=dev)
+            i = (g - (ends - rf)[idx]).to(torch.float64)
+            fn = rf[idx].to(torch.float64)
+            phone = idx // S
+            s = (idx % S + 1).to(torch.float64)
+            pd = r.sum(-1).reshape(-1)[phone].to(torch.float64)
+            base = (torch.cumsum(r, -1) - r).reshape(-1)[idx].to(torch.float64)
+            nine = torch.stack([(i + 1) / fn, (fn - i) / fn, fn, s, S + 1 - s, pd, fn / pd, (pd - i - base) / pd, (base + i + 1) / pd], dim=1)
+            rows = torch.cat([P.reshape(-1, Dl)[phone].to(torch.float64), nine], dim=1)
+            if affine:
+                rows = rows * sc + mn
+            utt = idx // (Nmax * S)
+            first = torch.cumsum(r.sum((1, 2)), 0) - r.sum((1, 2))                     # the batch index of every utterance's frame 0
+            res = torch.zeros((B, Tmax, W), dtype=torch.float32, device=dev)
+            res.view(-1, W)[utt * Tmax + (g - first[utt])] = rows.to(torch.float32)
+            return res
+
+        in_bytes = float(host_P.nbytes + host_d.nbytes + nph.nbytes)
+        out_bytes = 4.0 * B * Tmax * W
+        res = dict(path="frontend-config5", B=B, Tmax=Tmax, Nmax=Nmax, S=S, Dl=Dl, F=F, live_frames=live, hbm_peak_gbs=HBM_PEAK_GBS,
+                   block_rows=FH.BLOCK_ROWS, out_bytes=out_bytes, in_bytes=in_bytes)
+        res["fill_ms"] = gpu_time(lambda: out.zero_(), steps=20)     # a yardstick: torch's fill of the same output, stores alone
+        res["fill_hbm_frac"] = out_bytes / (res["fill_ms"] * 1e6) / HBM_PEAK_GBS
+        for affine, tag in ((False, "plain"), (True, "affine")):
+            a, b_ = (sc, mn) if affine else (None, None)
+            res["kernel_%s_ms" % tag] = gpu_time(lambda: FH.expand(P, d, n, FH.FULL, 0, None, a, b_, out), steps=20)
+            res["kernel_%s_hbm_frac" % tag] = (out_bytes + in_bytes) / (res["kernel_%s_ms" % tag] * 1e6) / HBM_PEAK_GBS
+            res["one_call_%s_wall_ms" % tag] = wall_time(lambda: FE.frame_features_batch(P, d, n, "full", min_frames=0, scale_=a, min_=b_, out=out,
+                                                                                         strict=False), steps=20, warmup=3)
+            res["composed_%s_ms" % tag] = gpu_time(lambda: composed(affine), steps=5, warmup=1)
+            res["composed_over_kernel_%s" % tag] = res["composed_%s_ms" % tag] / res["kernel_%s_ms" % tag]
+            FH.expand(P, d, n, FH.FULL, 0, None, a, b_, out)
+            res["equal_to_composed_%s" % tag] = bool(torch.equal(out, composed(affine)))
+        # the specification's per-frame loop (the reference's loop with the regular expressions taken out) on eight utterances, scaled
+        t0 = time.perf_counter()
+        for b in range(8):
+            m = FM.frame_features(host_P[b, :nph[b]], host_d[b, :nph[b]], "full", 0, scale_h, min_h, np.float32)
+            assert np.array_equal(m, out[b, :len(m)].cpu().numpy())
+        res["model_loop_8_utterances_ms"] = (time.perf_counter() - t0) * 1e3
+        res["model_loop_scaled_ms"] = res["model_loop_8_utterances_ms"] * live / float(frames[:8].sum())
+        res["note"] = ("float32 (B, 100, 416) phone-level features, 60 .. 100 phones x 5 states per utterance, int32 durations that add up to "
+                       "1000 .. 2000 frames, kind full, float32 (B, 2000, 425) out.  kernel_*_ms: HIP-event median of ONE launch of "
+                       "nnmk_frontend_expand on settled clocks, without and with the fused affine map; kernel_*_hbm_frac: the bytes of the whole "
+                       "padded output plus the inputs over that time as a fraction of 8 TB/s; fill_ms: torch's zero_() of the same output "
+                       "tensor, what stores alone reach.  one_call_*_wall_ms: wall clock of "
+                       "frame_features_batch(out=, strict=False) in a back-to-back loop.  composed_*_ms: the same padded result from torch "
+                       "operations on the same tensors (repeat_interleave with output_size, nine columns in float64, gather, cat, affine, one "
+                       "rounding, index_put into zeros); equal_to_composed_*: torch.equal of the two results.  model_loop_*: "
+                       "tools/frontend_model.py's per-frame Python loop on the first eight utterances (each compared with the kernel's rows, "
+                       "np.array_equal), scaled by live frames to the batch.  No counters were collected; no time is asserted anywhere")
+        emit(**res)
+        if not args.quick:
+            out_path = os.environ.get("NNMNKWII_FRONTEND_PROFILE") or os.path.join(ROOT, "profiles", "frontend.json")
             with open(out_path, "w") as fh:
                 json.dump(res, fh, indent=1, sort_keys=True)
                 fh.write("\n")
