@@ -48,6 +48,15 @@ extern "C" {
 #define MLPG_HIP_ERUNTIME (-2) /* HIP runtime error (launch, malloc, device)  */
 #define MLPG_HIP_ENOMEM (-3)   /* scratch allocation failed                   */
 
+/* Batch sizes.  Return code 0 means the WHOLE batch was done.  One kernel launch takes fewer than 2^32 threads; an entry whose
+ * kernel has a workgroup per batch item (the modulation-spectrum entries, mlpg_hip_trim_lengths, _gather_path, _fastdtw, the
+ * wave-per-system kernel of mlpg_hip_forward / _backward) walks a larger batch in several launches and still counts as one call.
+ * What cannot be cut refuses with MLPG_HIP_EINVAL, nothing written and no counter moved, in a text that names the limit:
+ * mlpg_hip_unit_mse_step in its one-launch form beyond 2^24 - 1 workgroups (8 per block of 8 utterances and group of 4 static
+ * dims), MLPG_HIP_ALGO_FIR / _CHUNK / _GENERIC by name beyond their grids (AUTO takes another kernel), mlpg_hip_delta_features,
+ * mlpg_hip_gmm_convert and the copy of one pass-through stream in mlpg_hip_forward_streams beyond 2^32 - 256 elements,
+ * mlpg_hip_gmm_estep and its siblings beyond 2^30 - 64 rows, mlpg_hip_column_stats beyond 2^26 - 4 columns. */
+
 /* variance modes */
 #define MLPG_HIP_VAR_FRAME 0   /* var is (B, Tmax, D)                         */
 #define MLPG_HIP_VAR_GLOBAL 1  /* var is (D,), tiled over frames (_mlpg.py:169-170) */

@@ -238,8 +238,23 @@ int check_algo(int in_dtype, int out_dtype, int algo, const Problem &p, const Wi
     set_error("MLPG_HIP_ALGO_CONST needs global or unit variances and 2-3 windows of extent <= 1 (var_mode %d, %d windows, T=%d)", p.var_mode, ws.nw, p.Tmax);
     return MLPG_HIP_EINVAL;
   }
+  if (algo == MLPG_HIP_ALGO_GENERIC && !generic_grid_fits(p)) {
+    set_error("MLPG_HIP_ALGO_GENERIC: B * sd * Tmax = %d * %d * %d cells are more than the %ld workgroups of 256 threads one launch takes: "
+              "a grid is 32 bits of threads", p.B, p.sd, p.Tmax, max_workgroups(256));
+    return MLPG_HIP_EINVAL;
+  }
+  if (algo == MLPG_HIP_ALGO_CHUNK && ws.mw >= 1 && ws.mw <= 2 && !chunk_grid_fits(p, ws)) {
+    set_error("MLPG_HIP_ALGO_CHUNK: B = %d, sd = %d, Tmax = %d take more than the %ld workgroups of 256 threads (%ld of 64 in the "
+              "reductions) one launch takes: a grid is 32 bits of threads", p.B, p.sd, p.Tmax, max_workgroups(256), max_workgroups(64));
+    return MLPG_HIP_EINVAL;
+  }
   if (algo == MLPG_HIP_ALGO_CHUNK && (in_dtype != out_dtype || !chunk_supported(p, ws))) {
     set_error("MLPG_HIP_ALGO_CHUNK: input dtype = output dtype, 1-3 windows of extent 1 or 2 (%d windows, extent %d)", ws.nw, ws.mw);
+    return MLPG_HIP_EINVAL;
+  }
+  if (algo == MLPG_HIP_ALGO_FIR && p.B >= 1 && p.sd >= 1 && !fir_grid_fits(p)) {
+    set_error("MLPG_HIP_ALGO_FIR: %ld workgroups of 512 threads are more than one launch takes (%ld): a grid is 32 bits of threads",
+              fir_workgroups(p), max_workgroups(512));
     return MLPG_HIP_EINVAL;
   }
   if (algo == MLPG_HIP_ALGO_FIR && !fir_shape_supported(p, ws, in_dtype, out_dtype)) {
@@ -454,6 +469,12 @@ __attribute__((visibility("default"))) int mlpg_hip_unit_mse_step(int device, vo
               Tmax, ws.q);
     return MLPG_HIP_EINVAL;
   }
+  if (unit_mse_workgroups(B, D / num_windows) > max_workgroups(256)) {  // (one launch with one arrival counter: not sliced)
+    set_error("unit_mse_step: %ld workgroups of 256 threads (8 per block of 8 utterances and group of 4 static dims) are more than one "
+              "launch takes (%ld): a grid is 32 bits of threads; split the batch", unit_mse_workgroups(B, D / num_windows),
+              max_workgroups(256));
+    return MLPG_HIP_EINVAL;
+  }
   if (!workspace || workspace_bytes < unit_mse_workspace_bytes(B, D / num_windows) || ((uintptr_t)workspace & 127)) {
     set_error("unit_mse_step: workspace of %zu bytes (128-byte aligned) needed, see mlpg_hip_unit_mse_workspace_bytes",
               unit_mse_workspace_bytes(B, D / num_windows));
@@ -544,6 +565,11 @@ __attribute__((visibility("default"))) int mlpg_hip_delta_features(int device, v
   WinSet ws;
   if (int rc = pack_windows(num_windows, win_l_h, win_u_h, win_coef_h, &ws)) return rc;
   if ((long)B * Tmax * D == 0) return 0;
+  if (!elementwise_grid_fits(B, Tmax, D)) {
+    set_error("delta_features: B * Tmax * D = %d * %d * %d elements are more than the %ld workgroups of 256 threads one launch takes: a "
+              "grid is 32 bits of threads", B, Tmax, D, max_workgroups(256));
+    return MLPG_HIP_EINVAL;
+  }
   if (!x || !out) {
     set_error("delta_features: NULL pointer");
     return MLPG_HIP_EINVAL;
@@ -726,6 +752,11 @@ __attribute__((visibility("default"))) int mlpg_hip_gmm_convert(int device, void
     return MLPG_HIP_EINVAL;
   }
   if (N == 0) return 0;
+  if ((double)N * Dy > (double)max_workgroups(256) * 256.0) {
+    set_error("gmm_convert: N * Dy = %lld * %d elements are more than the %ld workgroups of 256 threads one launch takes: a grid is 32 "
+              "bits of threads", (long long)N, Dy, max_workgroups(256));
+    return MLPG_HIP_EINVAL;
+  }
   if (!x || !mu_x || !mu_y || !A || !out || (!posterior && !mixture)) {
     set_error("gmm_convert: NULL pointer");
     return MLPG_HIP_EINVAL;
@@ -745,6 +776,11 @@ __attribute__((visibility("default"))) int mlpg_hip_gather_path(int device, void
     return MLPG_HIP_EINVAL;
   }
   if (N == 0 || Tout == 0 || D == 0) return 0;
+  if ((long)Tout * D > max_workgroups(256) * 256) {  // (utterances go in slices of launches; one utterance is one launch at least)
+    set_error("gather_path: Tout * D = %d * %d elements per utterance are more than the %ld workgroups of 256 threads one launch takes: a "
+              "grid is 32 bits of threads", Tout, D, max_workgroups(256));
+    return MLPG_HIP_EINVAL;
+  }
   if (!src || !path || !path_len || !out) {
     set_error("gather_path: NULL pointer");
     return MLPG_HIP_EINVAL;

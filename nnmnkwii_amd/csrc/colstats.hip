@@ -320,6 +320,12 @@ __attribute__((visibility("default"))) int mlpg_hip_column_stats(int device, voi
     set_error("%s: the batch is too large for one call (B = %d, Tmax = %d, D = %d)", who, B, Tmax, D);
     return MLPG_HIP_EINVAL;
   }
+  // the finish step takes a workgroup of 256 threads per kCsFinCols columns, whatever the batch (an empty one included)
+  if (((int64_t)D + kCsFinCols - 1) / kCsFinCols > kCsMaxBlocks) {
+    set_error("%s: D = %d columns are more than the %ld workgroups of 256 threads (%d columns each) one launch of the finish step takes",
+              who, D, kCsMaxBlocks, kCsFinCols);
+    return MLPG_HIP_EINVAL;
+  }
   if (int rc = check_device(who, device)) return rc;
   if (D == 0) return 0;
   if (!state_out) {

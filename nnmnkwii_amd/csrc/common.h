@@ -151,6 +151,8 @@ void *scratch(int device, hipStream_t stream, int slot, size_t bytes, unsigned l
 // launchers (one per translation unit)
 int launch_generic(hipStream_t s, int dtype, int out_dtype, bool backward, const Problem &p, const WinSet &w,
                    int device);
+bool generic_grid_fits(const Problem &p);                   // the natural-order kernel's grids are ones a launch takes
+bool elementwise_grid_fits(int B, int Tmax, int cols);      // ... and the one-thread-per-element grid of delta_features / copy_cols
 bool wave_supported(const Problem &p, const WinSet &w);
 int launch_wave(hipStream_t s, int dtype, int out_dtype, bool backward, const Problem &p, const WinSet &w,
                 int device);
@@ -165,6 +167,7 @@ int launch_strip(hipStream_t s, int dtype, int out_dtype, bool backward, const P
 // forward pass of several streams (p: the parent arrays, sd/D unused) -- per-frame variances, three windows of extent <= 1
 int launch_strip_multi(hipStream_t s, int dtype, const Problem &p, const WinSet &w, const StreamMap &sm, int device);
 bool unit_mse_supported(int Tmax, const WinSet &w);
+long unit_mse_workgroups(int B, int sd);  // the one-launch kernel's grid (256 threads per workgroup)
 size_t unit_mse_workspace_bytes(int B, int sd);
 int launch_unit_mse(hipStream_t s, int dtype, const Problem &p, const WinSet &w, const void *target, void *y_out,
                     double n_elems, double *loss, void *workspace);
@@ -180,6 +183,7 @@ bool const_preferred(const Problem &p, const WinSet &w);
 int launch_const(hipStream_t s, int dtype, int out_dtype, bool backward, const Problem &p, const WinSet &w, int device);
 int launch_const_multi(hipStream_t s, int dtype, const Problem &p, const WinSet &w, const StreamMap &sm, int device);
 bool chunk_supported(const Problem &p, const WinSet &w);
+bool chunk_grid_fits(const Problem &p, const WinSet &w);    // its grids are ones a launch takes (chunk_supported asks)
 bool chunk_preferred(const Problem &p, const WinSet &w, bool backward);
 int launch_chunk(hipStream_t s, int dtype, int out_dtype, bool backward, const Problem &p, const WinSet &w, int device);
 int launch_chunk_fwd_f64(hipStream_t s, const Problem &p, const WinSet &w, int device);
@@ -190,6 +194,8 @@ int launch_chunk_bwd_f32(hipStream_t s, const Problem &p, const WinSet &w, int d
 // fast enough (or its tap table cannot be built now: stream capture)
 constexpr int kFirNotApplicable = -2000;
 bool fir_shape_supported(const Problem &p, const WinSet &w, int in_dtype, int out_dtype);
+long fir_workgroups(const Problem &p);  // the largest grid the form launches for p (512 threads per workgroup)
+bool fir_grid_fits(const Problem &p);   // ... is one a launch takes (fir_shape_supported asks)
 bool fir_preferred(const Problem &p, bool backward);
 bool fir_table_ready(hipStream_t s, int device, const WinSet &w);
 void fir_shutdown();
@@ -269,6 +275,14 @@ int launch_colaffine(hipStream_t s, int in_dtype, int out_dtype, int mode, const
                      const int32_t *lengths, int B, int Tmax, int D, const double *a, const double *c);
 int launch_gather(hipStream_t s, int dtype, const void *src, const int32_t *path, const int32_t *path_len, int N,
                   int Tsrc, int path_stride, int D, int Tout, void *out);
+
+// A grid is 32 bits of threads: workgroups * threads per workgroup < 2^32, and a larger launch runs the threads that remain
+// modulo 2^32 and reports nothing (profiles/grid_limit_notes.md).  The most workgroups of `threads` threads one launch takes:
+// 2^22 - 1 of 1024, 2^23 - 1 of 512, 2^24 - 1 of 256, 2^26 - 1 of 64.
+constexpr long max_workgroups(int threads) { return ((1L << 32) - 1) / threads; }
+// The most batch items one launch takes when every item is `per_item` workgroups of `threads` threads (0: one item alone is over
+// the limit).  Launchers of one-workgroup-set-per-item kernels walk the batch in slices of this many items.
+inline long items_per_launch(long per_item, int threads) { return per_item > 0 ? max_workgroups(threads) / per_item : 0; }
 
 #define MLPG_HIP_CHECK(expr)                                                        \
   do {                                                                              \

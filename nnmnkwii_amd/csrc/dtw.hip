@@ -76,6 +76,7 @@ int launch_gmm_convert(hipStream_t s, const double *x, const double *post, const
                        const double *mu_y, const double *A, long N, int D, int Dy, int M, double *out) {
   const long total = N * Dy;
   if (total == 0) return 0;
+  // (mlpg_hip_gmm_convert refuses more than max_workgroups(256) workgroups before it selects a device)
   hipLaunchKernelGGL(gmm_convert_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, post, mix, mu_x, mu_y, A,
                      N, D, Dy, M, out);
   MLPG_HIP_CHECK(hipGetLastError());
@@ -83,30 +84,45 @@ int launch_gmm_convert(hipStream_t s, const double *x, const double *post, const
 }
 
 int launch_trim(hipStream_t s, int dtype, const void *X, int N, int T, int D, double eps, int32_t *lengths) {
-  if (dtype == MLPG_HIP_F32)
-    hipLaunchKernelGGL(trim_kernel<float>, dim3(N), dim3(64), 0, s, (const float *)X, T, D, eps, lengths);
-  else
-    hipLaunchKernelGGL(trim_kernel<double>, dim3(N), dim3(64), 0, s, (const double *)X, T, D, eps, lengths);
-  MLPG_HIP_CHECK(hipGetLastError());
+  // one launch per slice of utterances, each under the grid's thread limit: the kernel sees a shorter batch at offset bases
+  const long step = items_per_launch(1, 64);
+  const size_t row = (size_t)T * D;
+  for (long n0 = 0; n0 < N; n0 += step) {
+    const unsigned cnt = (unsigned)(N - n0 < step ? N - n0 : step);
+    if (dtype == MLPG_HIP_F32)
+      hipLaunchKernelGGL(trim_kernel<float>, dim3(cnt), dim3(64), 0, s, (const float *)X + (size_t)n0 * row, T, D, eps, lengths + n0);
+    else
+      hipLaunchKernelGGL(trim_kernel<double>, dim3(cnt), dim3(64), 0, s, (const double *)X + (size_t)n0 * row, T, D, eps, lengths + n0);
+    MLPG_HIP_CHECK(hipGetLastError());
+  }
   return 0;
 }
 
 int launch_gather(hipStream_t s, int dtype, const void *src, const int32_t *path, const int32_t *path_len, int N,
                   int Tsrc, int path_stride, int D, int Tout, void *out) {
   const long per = (long)Tout * D;
-  const long nblk = ((per + 255) / 256) * (long)N;
-  if (nblk > 0x7fffffffL) {
-    set_error("gather_path: problem too large (%ld blocks)", nblk);
+  const long nbx = (per + 255) / 256, step = items_per_launch(nbx, 256);
+  if (step < 1) {  // (mlpg_hip_gather_path asks the same before it selects a device)
+    set_error("gather_path: Tout * D = %ld elements per utterance are more than the %ld workgroups of 256 threads one launch takes", per,
+              max_workgroups(256));
     return MLPG_HIP_EINVAL;
   }
-  dim3 grid((unsigned)nblk);
-  if (dtype == MLPG_HIP_F32)
-    hipLaunchKernelGGL(gather_kernel<float>, grid, dim3(256), 0, s, (const float *)src, path, path_len, Tsrc,
-                       path_stride, D, Tout, (float *)out);
-  else
-    hipLaunchKernelGGL(gather_kernel<double>, grid, dim3(256), 0, s, (const double *)src, path, path_len, Tsrc,
-                       path_stride, D, Tout, (double *)out);
-  MLPG_HIP_CHECK(hipGetLastError());
+  // one launch per slice of whole utterances, each under the grid's thread limit: the kernel sees a shorter batch at offset bases
+  const size_t isz = dtype == MLPG_HIP_F32 ? sizeof(float) : sizeof(double);
+  for (long n0 = 0; n0 < N; n0 += step) {
+    const long cnt = N - n0 < step ? N - n0 : step;
+    const dim3 grid((unsigned)(cnt * nbx));
+    const char *src_n = (const char *)src + (size_t)n0 * Tsrc * D * isz;
+    char *out_n = (char *)out + (size_t)n0 * per * isz;
+    const int32_t *path_n = path + (size_t)n0 * path_stride;
+    if (dtype == MLPG_HIP_F32)
+      hipLaunchKernelGGL(gather_kernel<float>, grid, dim3(256), 0, s, (const float *)src_n, path_n, path_len + n0, Tsrc,
+                         path_stride, D, Tout, (float *)out_n);
+    else
+      hipLaunchKernelGGL(gather_kernel<double>, grid, dim3(256), 0, s, (const double *)src_n, path_n, path_len + n0, Tsrc,
+                         path_stride, D, Tout, (double *)out_n);
+    MLPG_HIP_CHECK(hipGetLastError());
+  }
   return 0;
 }
 

@@ -984,8 +984,24 @@ int launch_one(hipStream_t s, const DtwParams &p, int N, size_t lds) {
                                        (int)lds));
     if (device >= 0 && device < kMaxDevices) attr_set[device] = lds;
   }
-  hipLaunchKernelGGL((fastdtw_kernel<kThreads, TIE>), dim3(N), dim3(kThreads), lds, s, p);
-  MLPG_HIP_CHECK(hipGetLastError());
+  // one launch per slice of pairs, each under the grid's thread limit: the kernel sees a shorter batch at offset bases
+  const long step = items_per_launch(1, kThreads);
+  const size_t pcap = (size_t)p.Tx + p.Ty;
+  for (long n0 = 0; n0 < N; n0 += step) {
+    DtwParams q = p;
+    q.N = (int)(N - n0 < step ? N - n0 : step);
+    q.X = p.X + (size_t)n0 * p.Tx * p.D;
+    q.Y = p.Y + (size_t)n0 * p.Ty * p.D;
+    q.lenx = p.lenx + n0;
+    q.leny = p.leny + n0;
+    q.path_i = p.path_i + (size_t)n0 * pcap;
+    q.path_j = p.path_j + (size_t)n0 * pcap;
+    q.path_len = p.path_len + n0;
+    q.cost = p.cost + n0;
+    q.pyr = p.pyr + (size_t)n0 * p.pyr_stride;
+    hipLaunchKernelGGL((fastdtw_kernel<kThreads, TIE>), dim3((unsigned)q.N), dim3(kThreads), lds, s, q);
+    MLPG_HIP_CHECK(hipGetLastError());
+  }
   return 0;
 }
 

@@ -17,6 +17,8 @@ namespace {
 typedef double v4d __attribute__((ext_vector_type(4)));
 
 constexpr int kERows = 64;      // rows of X per E-step workgroup: 4 waves x one 16-row MFMA tile
+// the E-step's workgroups (256 threads) one launch takes: a grid is 32 bits of threads, a larger one runs truncated and reports nothing
+constexpr long long kEMaxBlocks = 16777215LL;  // 2^24 - 1
 constexpr int kMaxF = 128, kMaxK = 64;
 
 __device__ inline v4d mfma_f64(double a, double b, v4d c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
@@ -466,8 +468,13 @@ int check_gmm(const char *who, int device, int64_t N, int F, int K) {
     set_error("%s: the number of components must be in [1, %d] (got %d)", who, kMaxK, K);
     return MLPG_HIP_EINVAL;
   }
-  if (N < 0 || (N + kERows - 1) / kERows > 2147483647LL) {
+  if (N < 0) {
     set_error("%s: bad number of rows (%lld)", who, (long long)N);
+    return MLPG_HIP_EINVAL;
+  }
+  if ((N + kERows - 1) / kERows > kEMaxBlocks) {
+    set_error("%s: %lld rows are more than the %lld workgroups of 256 threads (%d rows each) one launch of the E-step takes: a grid is "
+              "32 bits of threads", who, (long long)N, kEMaxBlocks, kERows);
     return MLPG_HIP_EINVAL;
   }
   if (int rc = check_device(who, device)) return rc;
@@ -488,7 +495,7 @@ int check_workspace(const char *who, const void *workspace, size_t bytes, int64_
 extern "C" {
 
 __attribute__((visibility("default"))) size_t mlpg_hip_gmm_workspace_bytes(int64_t N, int F, int K) {
-  if (N < 0 || F < 1 || F > kMaxF || K < 1 || K > kMaxK || (N + kERows - 1) / kERows > 2147483647LL) return 0;
+  if (N < 0 || F < 1 || F > kMaxF || K < 1 || K > kMaxK || (N + kERows - 1) / kERows > kEMaxBlocks) return 0;
   return gmm_workspace_bytes((long)N, F, K);
 }
 

@@ -758,8 +758,19 @@ bool fir_shape_supported(const Problem &p, const WinSet &ws, int in_dtype, int o
   if (ws.nw < 1 || ws.nw > kMaxNw || ws.mw > kEXT || ws.l[0] != 0 || ws.u[0] != 0 || ws.c[ws.off[0]] == 0.0) return false;
   if (p.pitch && p.pitch != p.sd) return false;
   if (p.Tmax < 2 * kE + 2 * kH || p.B < 1 || p.sd < 1) return false;
-  return rows_fit_buffer(p);
+  return rows_fit_buffer(p) && fir_grid_fits(p);
 }
+
+// The larger of the two tile mappings' grids (grid_of), and the training step's one workgroup more, in 64 bits.
+long fir_workgroups(const Problem &p) {
+  using namespace fir;
+  const long ndg = (p.sd + 63) / 64, nsg = (long)p.B * ndg, nt = (p.Tmax + kTT - 1) / kTT;
+  return 2 * nsg + nsg * ((nt + kW - 1) / kW) + 1;
+}
+
+// A grid is 32 bits of threads (common.h, max_workgroups): a larger batch is not the FIR form's -- AUTO and the training step
+// take their other kernels, MLPG_HIP_ALGO_FIR by name is refused (check_algo).
+bool fir_grid_fits(const Problem &p) { return fir_workgroups(p) <= max_workgroups(fir::kW * 64); }
 
 // Does the FIR form serve this window set on this device: the tap table exists (it is built here, synchronously, on first use -- not
 // while `st` is being captured) and passed its decay test.  The ONE answer both mlpg_hip_unit_mse_step and mlpg_hip_unit_mse_form give.

@@ -207,6 +207,11 @@ template <int Q, typename TIN, typename TOUT, bool BWD>
 int launch_q(hipStream_t st, const Problem &p, const WinSet &w, int device) {
   const long S = (long)p.B * p.sd;
   if (S == 0 || p.Tmax == 0) return 0;
+  if (!generic_grid_fits(p)) {  // (the last kernel AUTO falls to: nothing else would take the call)
+    set_error("natural-order kernel: B * sd * Tmax = %d * %d * %d cells are more than the %ld workgroups of 256 threads one launch takes: "
+              "a grid is 32 bits of threads", p.B, p.sd, p.Tmax, max_workgroups(256));
+    return MLPG_HIP_EINVAL;
+  }
   const size_t bytes = sizeof(double) * (size_t)(Q + 2) * (size_t)p.Tmax * (size_t)S;
   double *sc = (double *)scratch(device, st, 0, bytes);
   if (!sc) return MLPG_HIP_ENOMEM;
@@ -307,10 +312,22 @@ int launch_stream_copy(hipStream_t st, const void *src, void *dst, size_t nbytes
   return 0;
 }
 
+// One thread per element, 256 per workgroup: the elements one launch of delta_kernel or copy_cols_kernel takes (a grid is 32
+// bits of threads: common.h, max_workgroups).  2^32 - 256 elements are 17 GB in float32.
+bool elementwise_grid_fits(int B, int Tmax, int cols) { return (double)B * Tmax * cols <= (double)(max_workgroups(256) * 256); }
+
+// ... and the natural-order kernel's three launches: one thread per cell (B * sd systems of Tmax frames), one per system
+bool generic_grid_fits(const Problem &p) { return elementwise_grid_fits(p.B, p.Tmax, p.sd); }
+
 int launch_copy_cols(hipStream_t st, int dtype, const void *src, long ld_src, const int32_t *lengths, int B, int Tmax,
                      int ncols, void *dst, long ld_dst) {
   const long total = (long)B * Tmax * ncols;
   if (total == 0) return 0;
+  if (!elementwise_grid_fits(B, Tmax, ncols)) {
+    set_error("copy of a pass-through stream: B * Tmax * columns = %ld elements are more than the %ld workgroups of 256 threads one launch "
+              "takes", total, max_workgroups(256));
+    return MLPG_HIP_EINVAL;
+  }
   const unsigned grid = (unsigned)((total + 255) / 256);
   if (dtype == MLPG_HIP_F32)
     hipLaunchKernelGGL(copy_cols_kernel<float>, dim3(grid), dim3(256), 0, st, (const float *)src, ld_src, lengths, B,
@@ -326,6 +343,11 @@ int launch_delta(hipStream_t st, int dtype, const void *x, const int32_t *length
                  const WinSet &w, void *out) {
   const long total = (long)B * Tmax * D;
   if (total == 0) return 0;
+  if (!elementwise_grid_fits(B, Tmax, D)) {  // (mlpg_hip_delta_features asks the same before it selects a device)
+    set_error("delta_features: B * Tmax * D = %ld elements are more than the %ld workgroups of 256 threads one launch takes", total,
+              max_workgroups(256));
+    return MLPG_HIP_EINVAL;
+  }
   const unsigned grid = (unsigned)((total + 255) / 256);
   if (dtype == MLPG_HIP_F32)
     hipLaunchKernelGGL(delta_kernel<float>, dim3(grid), dim3(256), 0, st, (const float *)x, lengths, B, Tmax, D, w,

@@ -96,6 +96,15 @@ void strip_scratch_forget(hipStream_t st, int device) {
   std::lock_guard<std::mutex> lk(g_clean_mu);
   g_clean[{device, st}].second = 0;
 }
+// The main kernel's grid is persistent; verdict_kernel takes a workgroup of 256 threads per 4 system groups, and a grid is 32 bits
+// of threads (common.h, max_workgroups).  Memory ends sooner: a group's record alone is 7 KB of scratch, 2^26 of them 480 GB.  Asked by
+// the three launchers before they take their scratch: MLPG_HIP_EINVAL, nothing enqueued.
+int strip_groups_fit(size_t nsg) {
+  if ((nsg + 3) / 4 <= (size_t)max_workgroups(256)) return 0;
+  set_error("strip kernel: %zu system groups are more than the %ld workgroups of 256 threads (4 groups each) one launch of the verdicts takes: "
+            "a grid is 32 bits of threads", nsg, max_workgroups(256));
+  return MLPG_HIP_EINVAL;
+}
 // scratch (control words + records) of one launch and whether its control area is known to be zero already
 void *strip_scratch(hipStream_t st, int device, size_t nsg, int R, bool *zero_ctrl) {
   const size_t ctrl = strip::ctrl_bytes((int)nsg, R);
@@ -190,6 +199,7 @@ int launch_strip_tr(hipStream_t st, int dtype, const Problem &p, const WinSet &w
   sm.tr_out = (int)((long)p.Tmax * p.ld_out);
   sm.tr_stat = p.ld_status;
   const size_t nsg = (size_t)(p.B + sm.tr_u - 1) / sm.tr_u;
+  if (int rc = strip_groups_fit(nsg)) return rc;
   bool zero_ctrl = true;
   void *sc = strip_scratch(st, device, nsg, R, &zero_ctrl);
   if (!sc) return MLPG_HIP_ENOMEM;
@@ -210,6 +220,7 @@ int launch_strip(hipStream_t st, int dtype, int out_dtype, bool backward, const 
   const int ndg = (p.sd + 63) / 64;
   const int dgw = (p.sd + ndg - 1) / ndg;
   const size_t nsg = (size_t)p.B * ndg;
+  if (int rc = strip_groups_fit(nsg)) return rc;
   bool zero_ctrl = true;
   void *sc = strip_scratch(st, device, nsg, R, &zero_ctrl);
   if (!sc) return MLPG_HIP_ENOMEM;
@@ -237,6 +248,7 @@ int launch_strip_multi(hipStream_t st, int dtype, const Problem &p, const WinSet
   const int ndg = (sm.total + 63) / 64;
   const int dgw = 64;  // full groups first: 66 dims = 64 + 2, not 33 + 33 (a group costs its frames whatever its lanes)
   const size_t nsg = (size_t)p.B * ndg;
+  if (int rc = strip_groups_fit(nsg)) return rc;
   bool zero_ctrl = true;
   void *sc = strip_scratch(st, device, nsg, R, &zero_ctrl);
   if (!sc) return MLPG_HIP_ENOMEM;

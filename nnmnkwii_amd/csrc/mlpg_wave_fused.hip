@@ -320,6 +320,10 @@ bool unit_mse_supported(int Tmax, const WinSet &ws) {
 // Workspace (caller-owned, so that the call allocates nothing and can be captured into a graph): the arrival counter on
 // the first 128-byte line (a fixed place: one workspace serves calls of different shapes), then one double per workgroup.  The counter must be zero when the kernel starts; the
 // kernel leaves it zero, so the caller zeroes a fresh workspace ONCE.
+// The launch's grid, in 64 bits: 8 workgroups per block of 8 utterances and group of kG static dims (mlpg_hip_unit_mse_step refuses
+// more than max_workgroups(kG * 64) of them -- the arrival counter and the last workgroup's sum belong to ONE launch).
+long unit_mse_workgroups(int B, int sd) { return (long)((B + 7L) / 8) * ((sd + kG - 1) / kG) * 8; }
+
 size_t unit_mse_workspace_bytes(int B, int sd) {
   const size_t nblocks = (size_t)((B + 7) / 8) * ((sd + kG - 1) / kG) * 8;
   return (nblocks * sizeof(double) + 127) / 128 * 128 + 128;

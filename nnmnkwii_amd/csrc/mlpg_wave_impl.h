@@ -746,13 +746,32 @@ template <int M, typename TIN, typename TOUT, bool BWD, bool DMA, int VM>
 int launch_k(hipStream_t st, const Problem &p, const WinSet &ws) {
   constexpr int MINW = (M <= 16) ? 2 : 1;
   const int ngrp = (p.sd + kG - 1) / kG;
-  const int nslots = ((p.B + 7) / 8) * ngrp;
   constexpr size_t lds = 2 * (size_t)tile_bytes<M, TIN>();
   auto kern = wave_kernel<M, MINW, TIN, TOUT, BWD, DMA, VM>;
+  // one launch per slice of whole blocks of 8 utterances (ngrp * 8 workgroups each), every slice under the grid's thread limit:
+  // the kernel sees a shorter batch at offset bases (a multiple of 8 utterances on: every alignment the launch was chosen by holds)
+  const long step = 8 * items_per_launch((long)ngrp * 8, kG * 64);
+  if (step < 1) {
+    set_error("wave kernel: %d static dims take %ld workgroups of %d threads per block of 8 utterances, more than one launch takes (%ld)",
+              p.sd, (long)ngrp * 8, kG * 64, max_workgroups(kG * 64));
+    return MLPG_HIP_EINVAL;
+  }
   MLPG_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   note_launch(kCountWave);
-  hipLaunchKernelGGL(kern, dim3(nslots * 8), dim3(kG * 64), lds, st, p, ws, ngrp, nslots);
-  MLPG_HIP_CHECK(hipGetLastError());
+  for (long b0 = 0; b0 < p.B; b0 += step) {
+    Problem q = p;
+    q.B = (int)(p.B - b0 < step ? p.B - b0 : step);
+    const size_t rows = (size_t)b0 * p.Tmax;
+    if (p.mean) q.mean = (const TIN *)p.mean + rows * p.ld_in;
+    if (p.var && VM == MLPG_HIP_VAR_FRAME) q.var = (const TIN *)p.var + rows * p.ld_in;
+    if (p.grad_out) q.grad_out = (const TIN *)p.grad_out + rows * p.ld_gout;
+    if (p.lengths) q.lengths = p.lengths + b0;
+    q.out = (TOUT *)p.out + rows * p.ld_out;
+    if (p.status) q.status = p.status + (size_t)b0 * p.ld_status;
+    const int nslots = ((q.B + 7) / 8) * ngrp;
+    hipLaunchKernelGGL(kern, dim3(nslots * 8), dim3(kG * 64), lds, st, q, ws, ngrp, nslots);
+    MLPG_HIP_CHECK(hipGetLastError());
+  }
   return 0;
 }
 

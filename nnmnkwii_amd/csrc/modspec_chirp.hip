@@ -271,8 +271,26 @@ template <int MODE>
 int launch_mode(hipStream_t st, const ChirpArgs &p, size_t lds) {
   auto kern = modspec_chirp_kernel<MODE>;
   MLPG_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)(p.B * ((p.D + 1) / 2))), dim3(kFftThreads), lds, st, p);
-  MLPG_HIP_CHECK(hipGetLastError());
+  // one launch per slice of whole sequences, each under the grid's thread limit: the kernel sees a shorter batch at offset bases
+  const long npair = (p.D + 1) / 2, step = items_per_launch(npair, kFftThreads);
+  if (step < 1) {
+    set_error("modspec: ceil(D / 2) = %ld workgroups of %d threads per sequence are more than one launch takes (%ld)", npair,
+              kFftThreads, max_workgroups(kFftThreads));
+    return MLPG_HIP_EINVAL;
+  }
+  const size_t nb = (size_t)p.n / 2 + 1, D = (size_t)p.D;
+  const size_t out_rows = MODE == kModeSpec ? nb : MODE == kModeInverse ? (size_t)p.n : (size_t)p.T;
+  for (long b0 = 0; b0 < p.B; b0 += step) {
+    ChirpArgs q = p;
+    q.B = (int)(p.B - b0 < step ? p.B - b0 : step);
+    if (p.x) q.x = p.x + (size_t)b0 * p.T * D;
+    if (p.ms) q.ms = p.ms + (size_t)b0 * nb * D;
+    if (p.ph) q.ph = p.ph + (size_t)b0 * nb * D * 2;
+    if (p.out_ph) q.out_ph = p.out_ph + (size_t)b0 * nb * D * 2;
+    q.out = p.out + (size_t)b0 * out_rows * D;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(q.B * npair)), dim3(kFftThreads), lds, st, q);
+    MLPG_HIP_CHECK(hipGetLastError());
+  }
   return 0;
 }
 

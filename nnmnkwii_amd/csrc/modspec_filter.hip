@@ -123,8 +123,22 @@ int launch_filter_typed(hipStream_t st, const FilterArgs &p) {
   const size_t lds = sizeof(Cplx) * ((size_t)padded_len(p.n) + (size_t)p.n);  // data + per-pass twiddle tables (< n entries)
   auto kern = modspec_filter_kernel<TX>;
   MLPG_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)(p.B * ((p.D + 1) / 2))), dim3(kFftThreads), lds, st, p);
-  MLPG_HIP_CHECK(hipGetLastError());
+  // one launch per slice of whole utterances, each under the grid's thread limit: the kernel sees a shorter batch at offset bases
+  const long npair = (p.D + 1) / 2, step = items_per_launch(npair, kFftThreads);
+  if (step < 1) {
+    set_error("modspec_filter: ceil(D / 2) = %ld workgroups of %d threads per utterance are more than one launch takes (%ld)", npair,
+              kFftThreads, max_workgroups(kFftThreads));
+    return MLPG_HIP_EINVAL;
+  }
+  for (long b0 = 0; b0 < p.B; b0 += step) {
+    FilterArgs q = p;
+    q.B = (int)(p.B - b0 < step ? p.B - b0 : step);
+    q.x = (const TX *)p.x + (size_t)b0 * p.T * p.ld_x;
+    q.out = (TX *)p.out + (size_t)b0 * p.T * p.ld_out;
+    if (p.lengths) q.lengths = p.lengths + b0;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(q.B * npair)), dim3(kFftThreads), lds, st, q);
+    MLPG_HIP_CHECK(hipGetLastError());
+  }
   return 0;
 }
 

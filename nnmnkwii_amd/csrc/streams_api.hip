@@ -447,8 +447,13 @@ __attribute__((visibility("default"))) int mlpg_hip_forward_streams(
   plan_streams(c, algo, mean, out, wsets, &plan);
   for (int i = 0; i < plan.nruns; ++i) {
     const StreamRun &r = plan.run[i];
-    if (c.streams[r.k].num_windows > 0)
+    if (c.streams[r.k].num_windows > 0) {
       if (int rc = check_stream_algo(who, r.k, dtype, r.algo, r.p, wsets[r.k])) return rc;
+    } else if (!elementwise_grid_fits(c.B, c.Tmax, r.p.sd)) {  // (a pass-through stream: one launch of copy_cols, a thread per element)
+      set_error("%s: stream %d: B * Tmax * static_dim = %d * %d * %d elements to copy are more than the %ld workgroups of 256 threads one "
+                "launch takes: a grid is 32 bits of threads", who, r.k, c.B, c.Tmax, r.p.sd, max_workgroups(256));
+      return MLPG_HIP_EINVAL;
+    }
   }
   DeviceGuard g(who, device);
   if (g.rc) return g.rc;

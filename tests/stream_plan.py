@@ -7,7 +7,8 @@ A stream is a dict with in_col, out_col, static_dim, num_windows, win_first (mlp
 packed (l[], u[], coeff[]) of include/mlpg_hip.h.  The support and preference predicates below restate csrc/mlpg_*.hip for
 the problems the stream tests build.  rows_fit_buffer is the one rule (csrc/common.h) that keeps the strip, constant-coefficient,
 chunked and FIR kernels inside the 2 GB window of their buffer descriptors: `ld` is the larger of the input's and the output's row
-stride, and the predicates that take it default to 0 (a problem that fits)."""
+stride, and the predicates that take it default to 0 (a problem that fits).  chunk_grid_fits, fir_grid_fits and generic_grid_fits
+restate the thread limit of a grid (common.h max_workgroups) for the chunked, FIR and natural-order kernels, which launch once."""
 import collections
 
 import numpy as np
@@ -90,17 +91,50 @@ def const_preferred(B, T, sd, var_mode, ws, ld=0):
     return (sd + ndg - 1) // ndg >= 32 and B * ndg >= 192
 
 
-def chunk_supported(ws, piece=False, T=0, ld=0):
-    return 1 <= ws.nw <= 3 and 1 <= ws.mw <= 2 and not piece and rows_fit_buffer(T, ld)
+def max_workgroups(threads):
+    """common.h max_workgroups: a grid is 32 bits of threads, so one launch takes (2^32 - 1) // threads workgroups."""
+    return ((1 << 32) - 1) // threads
+
+
+def chunk_grid_fits(B, T, sd, ws):
+    """mlpg_chunk.hip chunk_grid_fits: the two chunk passes take ceil(nsg K / 4) workgroups of 256 threads (K chunks of C = 20
+    frames with extents of 2, 16 otherwise), the reductions 2 nsg of 64, the verdicts ceil(B sd / 256) of 256."""
+    C = 20 if ws.mw == 2 else 16
+    dgw = min(sd, 64)
+    ndg = (sd + dgw - 1) // dgw if dgw else 0
+    nsg, K = B * ndg, (T + C - 1) // C
+    return (2 * nsg <= max_workgroups(64) and (nsg * K + 3) // 4 <= max_workgroups(256)
+            and (B * sd + 255) // 256 <= max_workgroups(256))
+
+
+def chunk_supported(ws, piece=False, T=0, ld=0, B=0, sd=0):
+    return 1 <= ws.nw <= 3 and 1 <= ws.mw <= 2 and not piece and rows_fit_buffer(T, ld) and chunk_grid_fits(B, T, sd, ws)
 
 
 def chunk_preferred(B, T, sd, ws, ld=0):
-    return chunk_supported(ws, T=T, ld=ld) and ws.mw == 2 and B * sd >= 64 and T >= 64
+    return chunk_supported(ws, T=T, ld=ld, B=B, sd=sd) and ws.mw == 2 and B * sd >= 64 and T >= 64
+
+
+def fir_workgroups(B, T, sd):
+    """mlpg_fir.hip fir_workgroups: the larger of the form's two grids, with the training step's one workgroup more -- nsg = B
+    ceil(sd / 64) system groups, nt = ceil(T / 32) tiles of frames, 8 wavefronts (512 threads) per workgroup."""
+    nsg, nt = B * ((sd + 63) // 64), (T + 31) // 32
+    return 2 * nsg + nsg * ((nt + 7) // 8) + 1
+
+
+def fir_grid_fits(B, T, sd):
+    return fir_workgroups(B, T, sd) <= max_workgroups(512)
 
 
 def fir_shape_supported(B, T, sd, dtype, var_mode, has_lengths, ws, piece=False, ld=0):
     return (dtype == F32 and var_mode == VAR_UNIT and not has_lengths and 1 <= ws.nw <= 3 and ws.mw <= 2 and ws.l[0] == 0
-            and ws.u[0] == 0 and ws.c0 != 0.0 and not piece and T >= 96 and B >= 1 and sd >= 1 and rows_fit_buffer(T, ld))
+            and ws.u[0] == 0 and ws.c0 != 0.0 and not piece and T >= 96 and B >= 1 and sd >= 1 and rows_fit_buffer(T, ld)
+            and fir_grid_fits(B, T, sd))
+
+
+def generic_grid_fits(B, T, sd):
+    """mlpg_generic.hip generic_grid_fits: one thread per cell of the B * sd systems of T frames, 256 per workgroup."""
+    return B * T * sd <= max_workgroups(256) * 256
 
 
 # ---- the plan
@@ -200,7 +234,9 @@ def solo_kind(s, ws, algo, var_mode, dtype, B, T, has_lengths, ld, sd, piece):
         raise Refused("MLPG_HIP_ALGO_STRIP")
     if algo == CONST and not const_supported(B, T, sd, var_mode, ws, ld=ld):
         raise Refused("MLPG_HIP_ALGO_CONST")
-    if algo == CHUNK and not chunk_supported(ws, T=T, ld=ld):
+    if algo == GENERIC and not generic_grid_fits(B, T, sd):
+        raise Refused("MLPG_HIP_ALGO_GENERIC")
+    if algo == CHUNK and not chunk_supported(ws, T=T, ld=ld, B=B, sd=sd):
         raise Refused("MLPG_HIP_ALGO_CHUNK")
     if algo == FIR and not fir_shape_supported(B, T, sd, dtype, var_mode, has_lengths, ws, ld=ld):
         raise Refused("MLPG_HIP_ALGO_FIR")

@@ -464,3 +464,113 @@ def test_header_constants_match_the_python_binding():
              "DIST_SCALED_SQL2_NP": _hip.DIST_SCALED_SQL2_NP, "TIE_FIRST_MIN": _hip.TIE_FIRST_MIN, "TIE_DIAG_LAST": _hip.TIE_DIAG_LAST}
     for name, val in pairs.items():
         assert defs.get(name) == val, (name, defs.get(name), val)
+
+
+def test_grids_beyond_the_thread_limit_are_refused_before_the_runtime_is_touched(L):
+    """A grid is 32 bits of threads (workgroups * threads per workgroup < 2^32); a larger launch would run truncated and report
+    nothing.  The entries that cannot cut their batch refuse it before a device is selected, the limit named.  For each: the call AT
+    the bound passes the check (the refusal that comes next answers: a NULL pointer, a bad device, the second stream), one item more
+    is refused.  Fake pointers throughout (a call that got as far as a launch would fault); no counter moves."""
+    from nnmnkwii_amd._hip import StreamDesc
+    fake = ctypes.c_void_p(64)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    c0 = [L.mlpg_hip_launch_count(k) for k in range(44)]
+    err = lambda: L.mlpg_hip_last_error().decode()  # noqa: E731
+    most = ((1 << 24) - 1) * 256                                      # elements of a one-thread-per-element launch: 2^32 - 256
+    wl, wu, wc = np.array([0], dtype=np.int32), np.array([0], dtype=np.int32), np.array([1.0])
+    # mlpg_hip_delta_features: B * Tmax * D elements
+    assert L.mlpg_hip_delta_features(0, None, 0, None, None, (1 << 24) - 1, 256, 1, 1, p(wl), p(wu), p(wc), None) == -1
+    assert "NULL pointer" in err()
+    assert L.mlpg_hip_delta_features(0, None, 0, None, None, 1 << 24, 256, 1, 1, p(wl), p(wu), p(wc), None) == -1
+    assert "16777215 workgroups of 256 threads" in err()
+    # mlpg_hip_gmm_convert: N * Dy elements
+    assert L.mlpg_hip_gmm_convert(0, None, None, None, None, None, None, None, most // 256, 4, 256, 2, None) == -1 and "NULL pointer" in err()
+    assert L.mlpg_hip_gmm_convert(0, None, None, None, None, None, None, None, most // 256 + 1, 4, 256, 2, None) == -1
+    assert "16777215 workgroups of 256 threads" in err()
+    # mlpg_hip_gather_path walks the utterances in slices: only ONE utterance of more than a grid is refused
+    assert L.mlpg_hip_gather_path(0, None, 0, None, None, None, 1 << 30, 4, 4, 256, (1 << 24) - 1, None) == -1 and "NULL pointer" in err()
+    assert L.mlpg_hip_gather_path(0, None, 0, None, None, None, 1, 4, 4, 256, 1 << 24, None) == -1
+    assert "16777215 workgroups of 256 threads" in err()
+    # the float64 modulation-spectrum entries walk the sequences in slices: no batch is refused for its size (the device is asked next)
+    assert L.mlpg_hip_modspec(99, None, fake, (1 << 31) - 1, 2, 4, 2, 0, fake, None) == -1 and "bad device" in err()
+    # a kernel family asked for by name, through the stream plan: stream 0 at its bound passes (stream 1 is refused for another
+    # reason), one utterance more and stream 0 is refused for its grid.  FIR: 3 B + 1 workgroups of 512 threads at Tmax = 96;
+    # CHUNK: 2 B workgroups of 64 threads in its reductions; GENERIC: B * sd * Tmax cells, one thread each.
+    wl2 = np.array([0, 1, 2], dtype=np.int32)
+    wc2 = np.array([1.0, -0.5, 0.0, 0.5, 1.0, -8.0, 0.0, 8.0, -1.0])
+    static, delta, ext2 = (1, 0), (1, 1), (1, 2)                      # (num_windows, win_first)
+
+    def streams(algo, dtype, var_mode, B, Tmax, s0, s1, sd1=1):
+        tab = (StreamDesc * 2)(StreamDesc(0, 0, 1, *s0), StreamDesc(1, 1, sd1, *s1))
+        rc = L.mlpg_hip_forward_streams(0, None, dtype, algo, fake, fake, var_mode, 1 + sd1, None, B, Tmax, 2, ctypes.addressof(tab), 3,
+                                        p(wl2), p(wl2), p(wc2), fake, 1 + sd1, None)
+        return rc, err()
+    fir_most = ((1 << 23) - 2) // 3
+    rc, e = streams(7, 0, 2, fir_most, 96, static, delta)
+    assert rc == -1 and "stream 1: MLPG_HIP_ALGO_FIR" in e, e
+    rc, e = streams(7, 0, 2, fir_most + 1, 96, static, delta)
+    assert rc == -1 and "stream 0: MLPG_HIP_ALGO_FIR" in e and "8388607" in e, e
+    rc, e = streams(6, 1, 0, (1 << 25) - 1, 8, ext2, static)
+    assert rc == -1 and "stream 1: MLPG_HIP_ALGO_CHUNK" in e, e
+    rc, e = streams(6, 1, 0, 1 << 25, 8, ext2, static)
+    assert rc == -1 and "stream 0: MLPG_HIP_ALGO_CHUNK" in e and "67108863" in e, e
+    rc, e = streams(1, 1, 0, (1 << 24) - 1, 256, static, static, sd1=2)
+    assert rc == -1 and "stream 1: MLPG_HIP_ALGO_GENERIC" in e and "16777215" in e, e
+    rc, e = streams(1, 1, 0, 1 << 24, 256, static, static, sd1=2)
+    assert rc == -1 and "stream 0: MLPG_HIP_ALGO_GENERIC" in e and "16777215" in e, e
+    # a pass-through stream is ONE launch of the copy, a thread per element: stream 0 (one column) at 2^32 - 256 elements passes
+    # (stream 1 is refused for its family), one utterance more is refused for the copy's grid
+    rc, e = streams(3, 1, 0, (1 << 24) - 1, 256, (0, 0), ext2)
+    assert rc == -1 and "stream 1: MLPG_HIP_ALGO_STRIP" in e, e
+    rc, e = streams(3, 1, 0, 1 << 24, 256, (0, 0), ext2)
+    assert rc == -1 and "stream 0: " in e and "elements to copy" in e and "16777215 workgroups of 256 threads" in e, e
+    assert [L.mlpg_hip_launch_count(k) for k in range(44)] == c0
+
+
+def test_the_restated_plan_refuses_a_family_for_its_grid_where_the_library_does(L):
+    """tests/stream_plan.py restates chunk_grid_fits, fir_grid_fits and generic_grid_fits (csrc/mlpg_chunk.hip, mlpg_fir.hip,
+    mlpg_generic.hip).  A family by name, two streams, fake pointers: at the bound the library takes stream 0 and refuses stream 1
+    (a window set or a width the family does not take), one utterance more and it refuses stream 0 -- and the plan predicts a
+    launch of the family for stream 0 at the bound, and raises Refused with the family's name one over.  The bounds: FIR 3 B + 1 <=
+    2^23 - 1 workgroups at Tmax = 96; CHUNK 2 B <= 2^26 - 1 in its reductions, and ceil(B K / 4) <= 2^24 - 1 in its passes (K = 13
+    chunks of 20 frames at Tmax = 256: B = 5162220); GENERIC B * sd * Tmax <= 2^32 - 256 cells."""
+    import stream_plan as SP
+    from nnmnkwii_amd._hip import StreamDesc
+    fake = ctypes.c_void_p(64)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    c0 = [L.mlpg_hip_launch_count(k) for k in range(44)]
+    wl = np.array([0, 1, 2], dtype=np.int32)
+    wc = np.array([1.0, -0.5, 0.0, 0.5, 1.0, -8.0, 0.0, 8.0, -1.0])
+    static, delta, ext2 = 0, 1, 2                                       # win_first of the three one-window sets
+    assert 5162220 * 13 == 4 * ((1 << 24) - 1)
+    cases = [(SP.FIR, SP.F32, SP.VAR_UNIT, ((1 << 23) - 2) // 3, 96, static, delta, 1, SP.K_FIR),
+             (SP.CHUNK, SP.F64, SP.VAR_FRAME, (1 << 25) - 1, 8, ext2, static, 1, SP.K_CHUNK),
+             (SP.CHUNK, SP.F64, SP.VAR_FRAME, 5162220, 256, ext2, static, 1, SP.K_CHUNK),
+             (SP.GENERIC, SP.F64, SP.VAR_FRAME, (1 << 24) - 1, 256, static, static, 2, SP.K_GENERIC)]
+    for algo, dtype, var_mode, B_most, T, w0, w1, sd1, kind in cases:
+        name = "MLPG_HIP_ALGO_" + SP.ALGO_NAME[algo]
+        tab = (StreamDesc * 2)(StreamDesc(0, 0, 1, 1, w0), StreamDesc(1, 1, sd1, 1, w1))
+        ws0, ws1 = SP.Win(wl, wl, wc, w0, 1), SP.Win(wl, wl, wc, w1, 1)
+        for B, refused in ((B_most, 1), (B_most + 1, 0)):
+            rc = L.mlpg_hip_forward_streams(0, None, dtype, algo, fake, fake, var_mode, 1 + sd1, None, B, T, 2, ctypes.addressof(tab), 3,
+                                            p(wl), p(wl), p(wc), fake, 1 + sd1, None)
+            e = L.mlpg_hip_last_error().decode()
+            assert rc == -1 and "stream %d: %s" % (refused, name) in e, (name, B, e)
+            solo = lambda ws, sd: SP.solo_kind(None, ws, algo, var_mode, dtype, B, T, False, 1 + sd1, sd, False)  # noqa: E731
+            if refused == 1:
+                assert solo(ws0, 1) == kind, (name, B)
+                with pytest.raises(SP.Refused) as ei:
+                    solo(ws1, sd1)
+            else:
+                with pytest.raises(SP.Refused) as ei:
+                    solo(ws0, 1)
+            assert str(ei.value) == name
+    # the predicates themselves, at the bound and one over
+    w2 = SP.Win(wl, wl, wc, ext2, 1)
+    assert SP.fir_workgroups(2796202, 96, 1) == (1 << 23) - 1 and SP.fir_grid_fits(2796202, 96, 1) and not SP.fir_grid_fits(2796203, 96, 1)
+    assert SP.fir_grid_fits(2796202 // 2, 96, 128) and not SP.fir_grid_fits(2796202 // 2 + 1, 96, 128)    # two groups of dims
+    assert SP.chunk_grid_fits((1 << 25) - 1, 8, 1, w2) and not SP.chunk_grid_fits(1 << 25, 8, 1, w2)
+    assert SP.chunk_grid_fits(5162220, 256, 1, w2) and not SP.chunk_grid_fits(5162221, 256, 1, w2)
+    assert SP.chunk_preferred(5162220, 256, 1, w2) and not SP.chunk_preferred(5162221, 256, 1, w2)          # AUTO goes elsewhere
+    assert SP.generic_grid_fits((1 << 24) - 1, 256, 1) and not SP.generic_grid_fits(1 << 24, 256, 1)
+    assert [L.mlpg_hip_launch_count(k) for k in range(44)] == c0

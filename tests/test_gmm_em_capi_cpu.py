@@ -89,3 +89,18 @@ def test_workspace_size_follows_the_slice_rule(L):
     assert L.mlpg_hip_gmm_workspace_bytes(10 ** 8, 128, 64) < 1 << 30
     for N, F, K in [(-1, 3, 2), (10, 0, 2), (10, 129, 2), (10, 3, 0), (10, 3, 65)]:
         assert L.mlpg_hip_gmm_workspace_bytes(N, F, K) == 0
+
+
+def test_the_row_bound_is_the_grids_thread_limit(L):
+    """The E-step takes one workgroup of 256 threads per 64 rows, and a grid is 32 bits of threads: 2^24 - 1 workgroups, 2^30 - 64
+    rows.  At the bound the call passes the row check (the next refusal, the device's, answers); one row more is refused with the
+    limit named -- by the E-step, by the M-step that shares the rule, and by the workspace size.  Fake pointers, no counter moves."""
+    c0 = _counts(L)
+    most = ((1 << 24) - 1) * 64
+    for f in (estep, mstep):
+        assert f(L, N=most, device=16) == -1 and b"bad device" in L.mlpg_hip_last_error()
+        assert f(L, N=most + 1, device=16) == -1
+        err = L.mlpg_hip_last_error()
+        assert b"16777215 workgroups of 256 threads" in err and b"bad device" not in err, err
+    assert L.mlpg_hip_gmm_workspace_bytes(most, 5, 3) > 0 and L.mlpg_hip_gmm_workspace_bytes(most + 1, 5, 3) == 0
+    assert _counts(L) == c0

@@ -76,6 +76,21 @@ def test_column_stats_refusals_come_before_the_runtime_is_touched(L):
     assert _counts(L) == c0
 
 
+def test_column_stats_refuses_more_columns_than_the_finish_step_has_threads_for(L):
+    """The finish step takes one workgroup of 256 threads per 4 columns, and a grid is 32 bits of threads: 2^24 - 1 workgroups,
+    2^26 - 4 columns (the statistics kernel, one workgroup per 64 columns, would take 2^30).  At the bound the call passes the
+    check (the next refusal, the device's, answers); four columns more are refused with the limit named.  No counter moves."""
+    c0 = _counts(L)
+    most = 4 * ((1 << 24) - 1)
+    big = dict(B=1, Tmax=1, workspace_bytes=(1 << 62))
+    assert stats(L, D=most, ld_x=most, device=16, **big) == -1 and b"bad device" in L.mlpg_hip_last_error()
+    assert stats(L, D=most + 1, ld_x=most + 1, device=16, **big) == -1
+    assert b"16777215 workgroups of 256 threads" in L.mlpg_hip_last_error()
+    assert stats(L, D=most + 1, ld_x=most + 1, device=16, B=0, Tmax=1, workspace_bytes=0) == -1        # an empty batch has a finish step too
+    assert b"16777215 workgroups of 256 threads" in L.mlpg_hip_last_error()
+    assert _counts(L) == c0
+
+
 def test_column_affine_refusals_and_empty_batches(L):
     c0 = _counts(L)
     cases = [dict(in_dtype=2), dict(out_dtype=2), dict(out_dtype=-1), dict(mode=2), dict(mode=-1), dict(B=-1), dict(Tmax=-1),
