@@ -9,7 +9,7 @@ Two situations:
 
 * the reference package is importable: the hot-path callables are replaced IN PLACE on its modules
   (``nnmnkwii.paramgen.mlpg`` and friends, the autograd functions, the aligners, ``baseline.gmm.MLPG``,
-  ``delta_features`` / ``trim_zeros_frames`` / the modspec functions, ``meanvar`` / ``meanstd`` / ``minmax`` and the scalers, ``postfilters.merlin_post_filter``, the four functions of ``metrics``,
+  ``delta_features`` / ``trim_zeros_frames`` / ``interp1d`` / the modspec functions, ``meanvar`` / ``meanstd`` / ``minmax`` and the scalers, ``postfilters.merlin_post_filter``, the four functions of ``metrics``,
   ``util.apply_each2d_*``);
   everything else of the reference (datasets, frontend, IO ...) keeps working as before;
 * it is not: lightweight ``nnmnkwii`` / ``nnmnkwii.<sub>`` module objects are registered in
@@ -41,8 +41,9 @@ _SURFACE = {
     "nnmnkwii.autograd": {k: getattr(_autograd, k) for k in (
         "mlpg", "MLPG", "unit_variance_mlpg", "UnitVarianceMLPG", "modspec", "ModSpec")},
     "nnmnkwii.preprocessing": {k: getattr(_preprocessing, k) for k in (
-        "delta_features", "trim_zeros_frames", "modspec", "modphase", "inv_modspec", "modspec_smoothing") + _NORM},
+        "delta_features", "trim_zeros_frames", "modspec", "modphase", "inv_modspec", "modspec_smoothing", "interp1d") + _NORM},
     "nnmnkwii.preprocessing.generic": {k: getattr(_preprocessing, k) for k in ("delta_features", "trim_zeros_frames") + _NORM},
+    "nnmnkwii.preprocessing.f0": {"interp1d": _preprocessing.interp1d},
     "nnmnkwii.preprocessing.alignment": {k: getattr(_alignment, k) for k in ("DTWAligner", "IterativeDTWAligner")},
     "nnmnkwii.preprocessing.modspec": {k: getattr(_modspec, k) for k in (
         "modspec", "modphase", "inv_modspec", "modspec_smoothing")},

@@ -5,7 +5,8 @@ apply a ``(T, D) -> (T', D')`` function to every utterance of a zero-padded ``(N
 collect the results in a zero-padded ``(N, Tmax, D')`` float64 array.  When the function is one of this
 package's batched operations (``paramgen.mlpg``, ``preprocessing.delta_features``,
 ``postfilters.merlin_post_filter``, ``postfilters.modspec_post_filter``, ``preprocessing.modspec_smoothing``,
-``preprocessing.scale`` / ``inv_scale`` / ``minmax_scale`` / ``inv_minmax_scale``) the whole batch goes
+``preprocessing.scale`` / ``inv_scale`` / ``minmax_scale`` / ``inv_minmax_scale``, ``preprocessing.interp1d`` on batches
+of one column) the whole batch goes
 to the GPU in one call instead of N; any other callable is applied per utterance, as in the reference.
 """
 import inspect
@@ -15,7 +16,7 @@ import numpy as np
 from . import _hip
 from . import postfilters as _pf
 from .paramgen import _mlpg as _pg
-from .preprocessing import generic as _gen
+from .preprocessing import f0 as _f0, generic as _gen
 from .preprocessing.modspec import modspec_smoothing as _smoothing, modspec_smoothing_batch as _smoothing_batch
 
 
@@ -37,6 +38,9 @@ def _batched(func2d, X, lengths, args, kwargs):
         return batch(X, lengths=lengths, **kw)
     if func2d in (_gen.scale, _gen.inv_scale, _gen.minmax_scale, _gen.inv_minmax_scale) and not {"lengths", "out"} & set(kwargs):
         return func2d(X, *args, lengths=lengths, **kwargs)          # one mlpg_hip_column_affine launch
+    if func2d is _f0.interp1d and X.shape[2] == 1 and len(args) + len(kwargs) <= 1 and set(kwargs) <= {"kind"}:
+        # (the reference's interp1d takes one column; on a wider batch the per-utterance path raises its RuntimeError)
+        return _f0.interp1d_batch(X, lengths, *args, **kwargs)      # one nnmk_f0_interp launch
     if kwargs:
         return None
     if func2d is _pg.mlpg and len(args) == 2:

@@ -58,6 +58,11 @@
         one nnmk_frontend_expand launch against the same result composed from torch operations and against the specification's
         per-frame loop on eight utterances (scaled); milliseconds and the fraction of 8 TB/s; also written to
         profiles/frontend.json (NNMNKWII_FRONTEND_PROFILE names another file)
+  f0 : (only with --only f0) continuous F0 over a padded 512 x 2000 x 187 float32 batch, lengths in [1000, 2000], about 40 % of the lf0
+        column unvoiced in runs: one nnmk_f0_interp launch that fills the column and writes the V/UV flag, against torch's plain
+        copy and fill of the same bytes, the same result composed from torch operations, and the reference-style per-utterance
+        loop over host copies (scaled); milliseconds per call over windows of back-to-back calls with their spread; also written
+        to profiles/f0.json (NNMNKWII_F0_PROFILE names another file)
 
 Each line carries the GPU time (HIP events on the launch stream), the algorithmic bytes, GB/s, and a
 bounded CPU baseline from the oracle on the same host (the checker, timed like bench.py's cpu_baseline).
@@ -1346,6 +1351,146 @@ def _run(only, quick, device_index):
         emit(**res)
         if not args.quick:
             out_path = os.environ.get("NNMNKWII_FRONTEND_PROFILE") or os.path.join(ROOT, "profiles", "frontend.json")
+            with open(out_path, "w") as fh:
+                json.dump(res, fh, indent=1, sort_keys=True)
+                fh.write("\n")
+
+    # ---- f0: the lf0 column of a config-5 sized padded batch filled in place, the flag into the vuv column; only with --only f0 ----
+    if args.only and "f0" in args.only.split(","):
+        from nnmnkwii_amd import _f0_hip as F0H
+        from nnmnkwii_amd import preprocessing as PP
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import f0_model as F0M
+        B, Tlo, Thi, W, LF0, VUV = (32, 1000, 2000, 187, 180, 181) if args.quick else (512, 1000, 2000, 187, 180, 181)
+        rng = np.random.RandomState(1234)
+        Tmax = Thi
+        lens_h = rng.randint(Tlo, Thi + 1, size=B).astype(np.int32)
+        host_X = rng.randn(B, Tmax, W).astype(np.float32)
+        for b in range(B):                                   # log-F0 in voiced runs of about 30 frames, unvoiced runs of about 20
+            t, on = 0, rng.rand() < 0.6
+            while t < Tmax:
+                n = 1 + rng.geometric(1.0 / (30 if on else 20))
+                host_X[b, t:t + n, LF0] = (4.5 + rng.rand(min(n, Tmax - t))) if on else -1e10
+                t += n
+                on = not on
+        live = int(lens_h.sum())
+        unvoiced_share = float(np.mean([np.mean(host_X[b, :lens_h[b], LF0] <= 0) for b in range(B)]))
+        X0 = torch.from_numpy(host_X).to(dev)               # the batch as it arrives (read by every timed call)
+        X = X0.clone()                                      # the batch the results go into
+        Ld = torch.from_numpy(lens_h).to(dev)
+        src, dst, flag = X0[:, :, LF0:LF0 + 1], X[:, :, LF0:LF0 + 1], X[:, :, VUV:VUV + 1]
+
+        def composed():
+            """The same result from torch operations on the same tensors: (filled (B, Tmax), flag (B, Tmax))."""
+            x = X0[:, :, LF0].to(torch.float64)
+            t = torch.arange(Tmax, device=dev)[None]
+            L = Ld.to(torch.int64)[:, None]
+            alive = t < L
+            voiced = (x > 0) & alive
+            below = torch.cummax(torch.where(voiced, t, -1), 1).values
+            above = torch.flip(torch.cummin(torch.flip(torch.where(voiced, t, Tmax), [1]), 1).values, [1])
+            has_p, has_q = below >= 0, above < Tmax
+            a, b_ = torch.gather(x, 1, below.clamp(min=0)), torch.gather(x, 1, above.clamp(max=Tmax - 1))
+            a, b_ = torch.where(has_p, a, b_), torch.where(has_q, b_, a)
+            p, q = torch.where(has_p, below, 0), torch.where(has_q, above, L - 1)
+            lin = a + (b_ - a) * ((t - p).to(torch.float64) / (q - p).to(torch.float64))
+            keep = voiced | ~(has_p | has_q) | (L < 2)
+            y = torch.where(keep, x, torch.where((t == 0) | (t == L - 1), a, torch.where(x <= 0, lin, x)))
+            return torch.where(alive, y, 0.0).to(torch.float32), voiced.to(torch.float32)
+
+        def composed_into():
+            y, v = composed()
+            X[:, :, LF0], X[:, :, VUV] = y, v
+
+        def windows(fn, reps, n=7):
+            """Milliseconds per call over `n` windows of `reps` back-to-back calls between two events, after a settled warm-up."""
+            gpu_time(fn, steps=3)
+            out = []
+            for _ in range(n):
+                a, b_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(reps):
+                    fn()
+                b_.record()
+                torch.cuda.synchronize()
+                out.append(a.elapsed_time(b_) / reps)
+            return dict(median_ms=float(np.median(out)), min_ms=float(min(out)), max_ms=float(max(out)), reps=reps, windows=n)
+
+        alg_bytes = 4.0 * (3 * live + 2 * (B * Tmax - live))          # read x, write y and the flag; two zeros per pad frame
+        res = dict(path="f0-config5", B=B, Tmax=Tmax, W=W, live_frames=live, unvoiced_share=unvoiced_share, hbm_peak_gbs=HBM_PEAK_GBS,
+                   tile=F0H.TILE, alg_bytes=alg_bytes)
+        kern = lambda: F0H.interp(src, Ld, F0H.SLINEAR, dst, flag)    # noqa: E731
+        res["kernel"] = windows(kern, 200)
+        res["kernel_hbm_frac"] = alg_bytes / (res["kernel"]["median_ms"] * 1e6) / HBM_PEAK_GBS
+        # a yardstick: the same bytes moved by torch with no computation (a strided copy of the column, a strided fill of the flag's)
+        def plain():
+            dst.copy_(src)
+            flag.zero_()
+        res["plain_copy_and_fill"] = windows(plain, 200)
+        res["plain_over_kernel"] = res["plain_copy_and_fill"]["median_ms"] / res["kernel"]["median_ms"]
+        res["one_call_wall_ms"] = wall_time(lambda: PP.interp1d_batch(src, Ld, out=dst, vuv=flag), steps=200, warmup=10)
+        res["composed"] = windows(composed_into, 10, n=5)
+        res["composed_over_kernel"] = res["composed"]["median_ms"] / res["kernel"]["median_ms"]
+        kern()
+        got_y, got_v = X[:, :, LF0].clone(), X[:, :, VUV].clone()
+        want_y, want_v = composed()
+        res["equal_to_composed"] = bool(torch.equal(got_y, want_y) and torch.equal(got_v, want_v))
+        # in place, as a user calls it (once: a second call would find the gaps filled), against the call above
+        Xi = X0.clone()
+        PP.interp1d_batch(Xi[:, :, LF0:LF0 + 1], Ld, out=Xi[:, :, LF0:LF0 + 1], vuv=Xi[:, :, VUV:VUV + 1])
+        res["in_place_equal"] = bool(torch.equal(Xi[:, :, LF0], got_y) and torch.equal(Xi[:, :, VUV], got_v))
+        rest = [c for c in range(W) if c not in (LF0, VUV)]
+        res["other_columns_untouched"] = bool(torch.equal(Xi[:, :, rest], X0[:, :, rest]))
+        # the reference-style loop: per utterance a copy of the column to the host, SciPy, a copy back, the flag derived separately
+        try:
+            from scipy import interpolate
+        except ImportError:
+            interpolate = None
+        nloop = min(B, 32)
+        Xl = X0.clone()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for b in range(nloop):
+            n = int(lens_h[b])
+            f = Xl[b, :n, LF0].cpu().numpy()
+            flag_h = (f > 0).astype(np.float32)
+            c = f.copy()
+            idx = np.where(c > 0)[0]
+            if len(idx):
+                c[0], c[-1] = c[idx[0]], c[idx[-1]]
+                idx = np.where(c > 0)[0]
+                gaps = np.where(c <= 0)[0]
+                if interpolate is not None:
+                    c[gaps] = interpolate.interp1d(idx, c[idx], kind="slinear")(gaps)
+                else:
+                    c[gaps] = np.interp(gaps, idx, c[idx])
+            Xl[b, :n, LF0] = torch.from_numpy(c).to(dev)
+            Xl[b, :n, VUV] = torch.from_numpy(flag_h).to(dev)
+        torch.cuda.synchronize()
+        res["host_loop_utterances"] = nloop
+        res["host_loop_ms"] = (time.perf_counter() - t0) * 1e3
+        res["host_loop_scaled_ms"] = res["host_loop_ms"] * B / nloop
+        res["host_loop_uses_scipy"] = interpolate is not None
+        res["host_loop_max_abs_diff"] = max(float((Xl[b, :lens_h[b], LF0] - got_y[b, :lens_h[b]]).abs().max().item()) for b in range(nloop))
+        m = F0M.batch(host_X[:4, :, LF0], lens_h[:4])
+        res["equal_to_model_4_utterances"] = bool(np.array_equal(m[0], got_y[:4].cpu().numpy()) and np.array_equal(m[1], got_v[:4].cpu().numpy()))
+        res["note"] = ("float32 (B, 2000, 187) batch, lengths 1000 .. 2000, the lf0 column (180) in voiced runs of about 30 frames and "
+                       "unvoiced runs of about 20 written as -1e10; kind slinear; the filled column goes to column 180 and the flag to "
+                       "column 181 of a second tensor of the same layout, so that every timed call finds the same gaps (in place a second "
+                       "call would find them filled; in_place_equal: one in-place call gives the same bits).  kernel / "
+                       "plain_copy_and_fill / composed: milliseconds per call between two HIP events around `reps` back-to-back calls, "
+                       "median, least and most of `windows` such windows on settled clocks.  plain_copy_and_fill: torch's strided copy_ "
+                       "of the column plus zero_() of the flag's column, the bytes the kernel must move and no computation; "
+                       "kernel_hbm_frac: those algorithmic bytes over the kernel's time as a fraction of 8 TB/s -- with a row stride of "
+                       "748 bytes every 4-byte element costs a whole memory transaction, so this fraction says how little of the traffic "
+                       "is payload, not how busy the memory system is.  composed: the same result from torch operations on the same "
+                       "tensors (cummax, flip / cummin / flip, two gathers, wheres, float64 arithmetic); equal_to_composed: torch.equal.  "
+                       "host_loop: per utterance the column copied to the host, SciPy's interp1d over the knots, the result and the flag "
+                       "copied back, on the first utterances and scaled to the batch.  No counters were collected; no time is asserted "
+                       "anywhere")
+        emit(**res)
+        if not args.quick:
+            out_path = os.environ.get("NNMNKWII_F0_PROFILE") or os.path.join(ROOT, "profiles", "f0.json")
             with open(out_path, "w") as fh:
                 json.dump(res, fh, indent=1, sort_keys=True)
                 fh.write("\n")
