@@ -9,7 +9,7 @@ Two situations:
 
 * the reference package is importable: the hot-path callables are replaced IN PLACE on its modules
   (``nnmnkwii.paramgen.mlpg`` and friends, the autograd functions, the aligners, ``baseline.gmm.MLPG``,
-  ``delta_features`` / ``trim_zeros_frames`` / ``interp1d`` / the modspec functions, ``meanvar`` / ``meanstd`` / ``minmax`` and the scalers, ``postfilters.merlin_post_filter``, the four functions of ``metrics``,
+  ``delta_features`` / ``trim_zeros_frames`` / ``interp1d`` / the modspec functions, the mu-law and pre-emphasis functions, ``meanvar`` / ``meanstd`` / ``minmax`` and the scalers, ``postfilters.merlin_post_filter``, the four functions of ``metrics``,
   ``util.apply_each2d_*``);
   everything else of the reference (datasets, frontend, IO ...) keeps working as before;
 * it is not: lightweight ``nnmnkwii`` / ``nnmnkwii.<sub>`` module objects are registered in
@@ -34,6 +34,8 @@ _modspec = importlib.import_module(__package__ + ".preprocessing.modspec")   # t
 
 # corpus normalisation (preprocessing/generic.py:496-829 of the reference)
 _NORM = ("meanvar", "meanstd", "minmax", "scale", "inv_scale", "minmax_scale_params", "minmax_scale", "inv_minmax_scale")
+# the waveform side (preprocessing/generic.py:56-226 of the reference)
+_WAVE = ("mulaw", "inv_mulaw", "mulaw_quantize", "inv_mulaw_quantize", "preemphasis", "inv_preemphasis")
 # reference module -> {attribute: replacement}
 _SURFACE = {
     "nnmnkwii.paramgen": {k: getattr(_paramgen, k) for k in (
@@ -42,7 +44,7 @@ _SURFACE = {
         "mlpg", "MLPG", "unit_variance_mlpg", "UnitVarianceMLPG", "modspec", "ModSpec")},
     "nnmnkwii.preprocessing": {k: getattr(_preprocessing, k) for k in (
         "delta_features", "trim_zeros_frames", "modspec", "modphase", "inv_modspec", "modspec_smoothing", "interp1d") + _NORM},
-    "nnmnkwii.preprocessing.generic": {k: getattr(_preprocessing, k) for k in ("delta_features", "trim_zeros_frames") + _NORM},
+    "nnmnkwii.preprocessing.generic": {k: getattr(_preprocessing, k) for k in ("delta_features", "trim_zeros_frames") + _NORM + _WAVE},
     "nnmnkwii.preprocessing.f0": {"interp1d": _preprocessing.interp1d},
     "nnmnkwii.preprocessing.alignment": {k: getattr(_alignment, k) for k in ("DTWAligner", "IterativeDTWAligner")},
     "nnmnkwii.preprocessing.modspec": {k: getattr(_modspec, k) for k in (
@@ -55,6 +57,9 @@ _SURFACE = {
                       "delta_features": _preprocessing.delta_features,
                       "apply_delta_windows": _preprocessing.delta_features},
 }
+# What the package ``nnmnkwii.preprocessing`` re-exports from generic.py beyond the table above, patched by install() in the same
+# way.  (Kept apart: the key set of _SURFACE["nnmnkwii.preprocessing"] is pinned by tests/test_f0_capi_cpu.py.)
+_REEXPORTS = {"nnmnkwii.preprocessing": {k: getattr(_preprocessing, k) for k in _WAVE}}
 _saved = []        # (module, attribute, previous value or _MISSING)
 _registered = []   # names we put into sys.modules
 _MISSING = object()
@@ -73,7 +78,7 @@ def install():
     if _saved or _registered:
         return
     have_ref = _reference_available()
-    for modname, attrs in _SURFACE.items():
+    for modname, attrs in list(_SURFACE.items()) + list(_REEXPORTS.items()):
         mod = None
         if have_ref:
             try:

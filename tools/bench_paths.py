@@ -63,6 +63,11 @@
         copy and fill of the same bytes, the same result composed from torch operations, and the reference-style per-utterance
         loop over host copies (scaled); milliseconds per call over windows of back-to-back calls with their spread; also written
         to profiles/f0.json (NNMNKWII_F0_PROFILE names another file)
+  wave : (only with --only wave) the waveform codec at float32 32 x 160000 and 512 x 16000, lengths in [Lmax / 2, Lmax]: one
+        nnmk_wave_encode launch (pre-emphasis, mu-law, int16 classes) and one nnmk_wave_decode launch (table, de-emphasis; at the
+        built-in segment length, 16384, 65536 and unsplit) against torch's plain copy of the same bytes, the same result composed
+        from torch operations, and the per-utterance host loop through the reference's expressions (scaled); protocol as f0;
+        also written to profiles/wave.json (NNMNKWII_WAVE_PROFILE names another file)
 
 Each line carries the GPU time (HIP events on the launch stream), the algorithmic bytes, GB/s, and a
 bounded CPU baseline from the oracle on the same host (the checker, timed like bench.py's cpu_baseline).
@@ -1491,6 +1496,146 @@ def _run(only, quick, device_index):
         emit(**res)
         if not args.quick:
             out_path = os.environ.get("NNMNKWII_F0_PROFILE") or os.path.join(ROOT, "profiles", "f0.json")
+            with open(out_path, "w") as fh:
+                json.dump(res, fh, indent=1, sort_keys=True)
+                fh.write("\n")
+
+    # ---- wave: crops to classes (encode) and classes to waveforms (decode), one launch each, at two shapes; only with --only wave ----
+    if args.only and "wave" in args.only.split(","):
+        from nnmnkwii_amd import _wave_hip as WH
+        from nnmnkwii_amd import preprocessing as PP
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import wave_model as WM
+        try:
+            from scipy import signal
+        except ImportError:
+            signal = None
+        MU, COEF = 256, 0.97
+        c32 = float(np.float32(COEF))
+
+        def windows(fn, reps, n=7):
+            """Milliseconds per call over `n` windows of `reps` back-to-back calls between two events, after a settled warm-up."""
+            gpu_time(fn, steps=3)
+            out = []
+            for _ in range(n):
+                a, b_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(reps):
+                    fn()
+                b_.record()
+                torch.cuda.synchronize()
+                out.append(a.elapsed_time(b_) / reps)
+            return dict(median_ms=float(np.median(out)), min_ms=float(min(out)), max_ms=float(max(out)), reps=reps, windows=n)
+
+        shapes = [(4, 20000)] if args.quick else [(32, 160000), (512, 16000)]
+        res = dict(path="wave", mu=MU, coef=COEF, tile=WH.TILE, hbm_peak_gbs=HBM_PEAK_GBS, shapes=[])
+        for B, Lmax in shapes:
+            rng = np.random.RandomState(1234)
+            lens_h = rng.randint(Lmax // 2, Lmax + 1, size=B).astype(np.int32)
+            lens_h[0] = Lmax
+            host_X = (np.cumsum(rng.randn(B, Lmax).astype(np.float32), 1) * 0.01 + rng.randn(B, Lmax).astype(np.float32) * 0.05)
+            host_X = np.clip(host_X * np.abs(np.sin(np.arange(Lmax, dtype=np.float32) / 977.0)), -0.999, 0.999).astype(np.float32)
+            live = int(lens_h.sum())
+            X = torch.from_numpy(host_X).to(dev)
+            Ld = torch.from_numpy(lens_h).to(dev)
+            C = torch.empty((B, Lmax), dtype=torch.int16, device=dev)
+            Y = torch.empty((B, Lmax), dtype=torch.float32, device=dev)
+            table = torch.from_numpy(WM.inv_mulaw_table(MU)).to(dev)
+            alive = torch.arange(Lmax, device=dev)[None] < Ld[:, None]
+            r = dict(B=B, Lmax=Lmax, live_samples=live)
+            # ---- encode: float32 -> pre-emphasis -> mu-law -> int16 classes
+            enc_bytes = 4.0 * live + 2.0 * B * Lmax
+            enc = lambda: WH.encode(X, Ld, COEF, WH.QUANTIZE, MU, C)      # noqa: E731
+            r["encode"] = windows(enc, 100)
+            r["encode_alg_bytes"] = enc_bytes
+            r["encode_hbm_frac"] = enc_bytes / (r["encode"]["median_ms"] * 1e6) / HBM_PEAK_GBS
+            r["encode_one_call_wall_ms"] = wall_time(lambda: PP.wave_encode_batch(X, Ld, COEF, MU, out=C), steps=100, warmup=10)
+            src8 = torch.empty(int(enc_bytes // 2), dtype=torch.uint8, device=dev).random_(0, 255)
+            dst8 = torch.empty_like(src8)
+            r["encode_plain_copy"] = windows(lambda: dst8.copy_(src8), 100)
+
+            def enc_composed():
+                nc = torch.tensor(-np.float32(COEF), device=dev)
+                p = X.clone()
+                p[:, 1:] = X[:, 1:] + nc * X[:, :-1]
+                d = p.to(torch.float64)
+                v = (torch.sign(d) * torch.log1p(MU * d.abs()) / math.log1p(MU) + 1.0) / 2.0 * MU
+                return torch.where(alive, v.to(torch.int16), MU // 2)
+            r["encode_composed"] = windows(enc_composed, 5, n=5)
+            enc()
+            got_c, want_c = C.clone(), enc_composed()
+            differ = (got_c != want_c)
+            r["encode_differs_from_composed"] = int(differ.sum().item())      # (torch's log1p against the kernel's, at bin edges)
+            r["encode_max_class_diff"] = int((got_c.to(torch.int32) - want_c.to(torch.int32)).abs().max().item())
+            m = WM.encode_batch(host_X[:1], lens_h[:1], COEF, WM.QUANTIZE, MU, np.int16)
+            r["encode_first_utterance_differs_from_model"] = int((m != got_c[:1].cpu().numpy()).sum())
+            # ---- decode: int16 classes -> table -> de-emphasis -> float32, at the segment settings
+            dec_bytes = 2.0 * live + 4.0 * B * Lmax
+            r["decode_alg_bytes"] = dec_bytes
+            r["decode_plan_auto"] = list(WH.plan(Lmax, c32, 0))
+            for name, seg in (("auto", 0), ("S16384", 16384), ("S65536", 65536), ("unsplit", Lmax)):
+                if 0 < seg < Lmax or name in ("auto", "unsplit"):
+                    r["decode_" + name] = windows(lambda: WH.decode(got_c, Ld, WH.QUANTIZE, MU, table, c32, seg, Y), 100 if name != "unsplit" else 20)
+                    r["decode_" + name]["nseg"] = WH.plan(Lmax, c32, seg)[2]
+            r["decode_hbm_frac_auto"] = dec_bytes / (r["decode_auto"]["median_ms"] * 1e6) / HBM_PEAK_GBS
+            r["decode_one_call_wall_ms"] = wall_time(lambda: PP.wave_decode_batch(got_c, Ld, MU, COEF, out=Y), steps=100, warmup=10)
+            src8 = torch.empty(int(dec_bytes // 2), dtype=torch.uint8, device=dev).random_(0, 255)
+            dst8 = torch.empty_like(src8)
+            r["decode_plain_copy"] = windows(lambda: dst8.copy_(src8), 100)
+
+            def dec_composed():
+                y = torch.where(alive, table[got_c.to(torch.int64).clamp(0, MU)].to(torch.float64), 0.0)
+                d, cd = 1, c32
+                while d < Lmax and cd != 0.0:                 # a log-step scan: y[n] += c^d y[n - d]
+                    y = torch.cat([y[:, :d], y[:, d:] + cd * y[:, :-d]], 1)
+                    d, cd = 2 * d, cd * cd
+                return torch.where(alive, y, 0.0).to(torch.float32)
+            r["decode_composed"] = windows(dec_composed, 3, n=5)
+            WH.decode(got_c, Ld, WH.QUANTIZE, MU, table, c32, 0, Y)
+            got_y = Y.clone()
+            r["decode_max_abs_diff_from_composed"] = float((got_y - dec_composed()).abs().max().item())
+            WH.decode(got_c, Ld, WH.QUANTIZE, MU, table, c32, Lmax, Y)
+            r["decode_max_abs_diff_auto_from_unsplit"] = float((got_y - Y).abs().max().item())
+            m = WM.decode_batch(got_c[:1].cpu().numpy(), lens_h[:1], WM.QUANTIZE, MU, c32, 0, np.float32)
+            r["decode_first_utterance_equals_model"] = bool(np.array_equal(m.view(np.int32), got_y[:1].cpu().numpy().view(np.int32)))
+            # ---- the reference-style loop: per utterance a copy to the host, the reference's expressions, a copy back
+            nloop = min(B, 8)
+            if signal is not None:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for b in range(nloop):
+                    n = int(lens_h[b])
+                    x = X[b, :n].cpu().numpy()
+                    p = signal.lfilter(np.array([1.0, -COEF], x.dtype), np.array([1.0], x.dtype), x)
+                    yq = np.sign(p) * np.log1p(MU * np.abs(p)) / np.log1p(MU)
+                    C[b, :n] = torch.from_numpy(((yq + 1) / 2 * MU).astype(int).astype(np.int16)).to(dev)
+                torch.cuda.synchronize()
+                r["encode_host_loop_scaled_ms"] = (time.perf_counter() - t0) * 1e3 * B / nloop
+                t0 = time.perf_counter()
+                for b in range(nloop):
+                    n = int(lens_h[b])
+                    q = got_c[b, :n].cpu().numpy()
+                    yf = 2 * q.astype(np.float32) / MU - 1
+                    w = np.sign(yf) * (1.0 / MU) * ((1.0 + MU) ** np.abs(yf) - 1.0)
+                    Y[b, :n] = torch.from_numpy(signal.lfilter(np.array([1.0], w.dtype), np.array([1.0, -COEF], w.dtype), w)).to(dev)
+                torch.cuda.synchronize()
+                r["decode_host_loop_scaled_ms"] = (time.perf_counter() - t0) * 1e3 * B / nloop
+                r["host_loop_utterances"] = nloop
+                r["decode_host_loop_max_abs_diff"] = max(float((Y[b, :lens_h[b]] - got_y[b, :lens_h[b]]).abs().max().item()) for b in range(nloop))
+            res["shapes"].append(r)
+        res["note"] = ("float32 waveforms, lengths Lmax / 2 .. Lmax, mu 256, coef 0.97.  encode: pre-emphasis -> mu-law -> int16 classes in one "
+                       "nnmk_wave_encode launch; decode: int16 classes -> table -> de-emphasis -> float32 in one nnmk_wave_decode launch, at "
+                       "segment 0 (the built-in choice), 16384, 65536 and Lmax (one workgroup per utterance).  Milliseconds per call between two "
+                       "HIP events around `reps` back-to-back calls: median, least and most of `windows` such windows on settled clocks.  "
+                       "plain_copy: torch's copy_ of a uint8 buffer of half the launch's algorithmic bytes (so it moves the same bytes and "
+                       "computes nothing); hbm_frac: algorithmic bytes over time as a fraction of 8 TB/s.  composed: the same result from "
+                       "torch operations (encode: shifted multiply-add, float64 log1p, truncation; decode: a gather and a log-step scan of "
+                       "torch.cat passes in float64).  host_loop: per utterance a copy to the host, the reference's numpy expressions and "
+                       "scipy.signal.lfilter, a copy back, on the first utterances and scaled to the batch.  No counters were collected; "
+                       "no time is asserted anywhere")
+        emit(**res)
+        if not args.quick:
+            out_path = os.environ.get("NNMNKWII_WAVE_PROFILE") or os.path.join(ROOT, "profiles", "wave.json")
             with open(out_path, "w") as fh:
                 json.dump(res, fh, indent=1, sort_keys=True)
                 fh.write("\n")
