@@ -18,12 +18,15 @@ behind the Python signatures of r9y9/nnmnkwii's hot path.
     nnmnkwii_amd.preprocessing.wave  mulaw, inv_mulaw, mulaw_quantize, inv_mulaw_quantize, preemphasis, inv_preemphasis;
                                 wave_encode_batch, wave_decode_batch (waveform crops to classes and generated classes to waveforms
                                 over padded batches, one launch each; also exported from nnmnkwii_amd.preprocessing)
+    nnmnkwii_amd.preprocessing.frames  remove_zeros_frames, remove_zeros_frames_batch, joint_features_batch (the joint rows of a
+                                voice-conversion recipe: deltas, concatenation and zero-frame removal in three launches; also exported
+                                from nnmnkwii_amd.preprocessing)
     nnmnkwii_amd.frontend.merlin  frame_features, frame_features_batch (phone-level linguistic features and durations to the
                                 frame-level input matrix of an acoustic model), get_frame_feature_size, coarse_coding_table
 
 Everything numerical runs in hand-written HIP kernels (``csrc/``) behind the
 C ABI of ``include/mlpg_hip.h`` (the objective metrics: its extension header
-``include/nnmnkwii_metrics.h``; the frontend: ``include/nnmnkwii_frontend.h``; continuous F0: ``include/nnmnkwii_f0.h``; the waveform codec: ``include/nnmnkwii_wave.h``).  There is no CPU fallback: without the built
+``include/nnmnkwii_metrics.h``; the frontend: ``include/nnmnkwii_frontend.h``; continuous F0: ``include/nnmnkwii_f0.h``; the waveform codec: ``include/nnmnkwii_wave.h``; the joint rows: ``include/nnmnkwii_joint.h``).  There is no CPU fallback: without the built
 extension or without a GPU the calls raise ``HipExtensionError``.
 """
 from ._hip import HipExtensionError  # noqa: F401

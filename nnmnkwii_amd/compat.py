@@ -9,7 +9,7 @@ Two situations:
 
 * the reference package is importable: the hot-path callables are replaced IN PLACE on its modules
   (``nnmnkwii.paramgen.mlpg`` and friends, the autograd functions, the aligners, ``baseline.gmm.MLPG``,
-  ``delta_features`` / ``trim_zeros_frames`` / ``interp1d`` / the modspec functions, the mu-law and pre-emphasis functions, ``meanvar`` / ``meanstd`` / ``minmax`` and the scalers, ``postfilters.merlin_post_filter``, the four functions of ``metrics``,
+  ``delta_features`` / ``trim_zeros_frames`` / ``remove_zeros_frames`` / ``interp1d`` / the modspec functions, the mu-law and pre-emphasis functions, ``meanvar`` / ``meanstd`` / ``minmax`` and the scalers, ``postfilters.merlin_post_filter``, the four functions of ``metrics``,
   ``util.apply_each2d_*``);
   everything else of the reference (datasets, frontend, IO ...) keeps working as before;
 * it is not: lightweight ``nnmnkwii`` / ``nnmnkwii.<sub>`` module objects are registered in
@@ -60,6 +60,10 @@ _SURFACE = {
 # What the package ``nnmnkwii.preprocessing`` re-exports from generic.py beyond the table above, patched by install() in the same
 # way.  (Kept apart: the key set of _SURFACE["nnmnkwii.preprocessing"] is pinned by tests/test_f0_capi_cpu.py.)
 _REEXPORTS = {"nnmnkwii.preprocessing": {k: getattr(_preprocessing, k) for k in _WAVE}}
+# remove_zeros_frames under its three names in the reference (preprocessing/generic.py:335, re-exported by the package and by
+# nnmnkwii.util).  A table of its own: the key sets of the two above are pinned by the tests of the earlier extensions.
+_ROUTES = {m: {"remove_zeros_frames": _preprocessing.remove_zeros_frames}
+           for m in ("nnmnkwii.preprocessing", "nnmnkwii.preprocessing.generic", "nnmnkwii.util")}
 _saved = []        # (module, attribute, previous value or _MISSING)
 _registered = []   # names we put into sys.modules
 _MISSING = object()
@@ -78,7 +82,7 @@ def install():
     if _saved or _registered:
         return
     have_ref = _reference_available()
-    for modname, attrs in list(_SURFACE.items()) + list(_REEXPORTS.items()):
+    for modname, attrs in list(_SURFACE.items()) + list(_REEXPORTS.items()) + list(_ROUTES.items()):
         mod = None
         if have_ref:
             try:

@@ -108,6 +108,14 @@ class DTWAligner(object):
     -- the pairs are dealt in chunks over those devices from this one process
     (mlpg_hip_fastdtw_host_multi); default: the process's current GPU.
 
+    ``transform`` on two CUDA tensors (float32 / float64, one device) stays on
+    the device: it returns two CUDA tensors of the longer input's dtype with the
+    shape the numpy route gives, after one read-back of two integers (the
+    shortest and the longest path).  A ``dist`` that would have to be evaluated
+    on the host, and ``devices=``, raise ``ValueError`` there.
+    ``path_lengths_`` holds the aligned lengths after every call: a device int32
+    ``(N)`` tensor for tensors, a numpy array for numpy inputs.
+
     Attributes:
         dist (function): Distance function (default L2).
         radius (int): fastdtw radius.
@@ -208,14 +216,68 @@ class DTWAligner(object):
             return g.cpu().numpy().astype(dtype, copy=False)
         return pi, pj, plen, cost, lenx, leny, gather
 
+    def _transform_tensors(self, X, Y):
+        """transform() on two CUDA tensors: trim, fastdtw and the gathers on the device, the aligned batches returned as CUDA
+        tensors.  One read-back of two integers: the shortest path (the empty-pair error) and the longest (T_out)."""
+        torch = _hip.torch_mod()
+        for name, t in (("X", X), ("Y", Y)):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dim() == 3 and t.dtype in (torch.float32, torch.float64)):
+                raise ValueError("DTWAligner: with tensors, X and Y must both be float32 / float64 CUDA tensors of shape (N, T, D) "
+                                 "(%s is not)" % name)
+        if X.device != Y.device or X.shape[0] != Y.shape[0] or X.shape[2] != Y.shape[2]:
+            raise ValueError("DTWAligner: X and Y must be on one device and share N and D, got %s on %s and %s on %s"
+                             % (tuple(X.shape), X.device, tuple(Y.shape), Y.device))
+        if getattr(self, "devices", None) is not None:
+            raise ValueError("DTWAligner: `devices` deals host arrays over several GPUs; tensors are aligned on their own device")
+        resolved = _resolve_dist(self.dist)
+        if resolved is None:
+            raise ValueError("DTWAligner: this `dist` is none of the distances the kernel evaluates itself, so it would have to be "
+                             "called on the host once per window cell: pass numpy arrays for that")
+        dist_kind, dist_scale = resolved
+        if dist_kind != _hip.DIST_L2 and X.shape[2] > _NP_MAX_DIMS:
+            raise ValueError("DTWAligner: the kernel reproduces numpy's summation order of this `dist` for at most %d feature dims "
+                             "(got %d), so it would have to be evaluated on the host: pass numpy arrays for that" % (_NP_MAX_DIMS, X.shape[2]))
+        tie = _hip.TIE_FIRST_MIN if getattr(self, "tie_rule", "first") == "first" else _hip.TIE_DIAG_LAST
+        longer = X if X.shape[1] > Y.shape[1] else Y       # alignment.py:44
+        N = X.shape[0]
+        if N == 0:
+            self.path_lengths_ = torch.zeros((0,), dtype=torch.int32, device=X.device)
+            return torch.zeros_like(longer), torch.zeros_like(longer)
+        _hip.require_gpu(X.device)
+        with torch.cuda.device(X.device):
+            Xd, Yd = X.contiguous(), Y.contiguous()
+            lenx = _hip.trim_lengths(Xd)                   # :46-49
+            leny = _hip.trim_lengths(Yd)
+            path_i, path_j, path_len, cost = _hip.fastdtw_l2(Xd.to(torch.float64), Yd.to(torch.float64), lenx, leny, self.radius, dist_kind,
+                                                             dist_scale, tie)   # :50
+            self.path_lengths_ = path_len
+            shortest, longest = torch.stack((path_len.min(), path_len.max())).tolist()
+            if shortest <= 0:
+                bad = int(torch.nonzero(path_len <= 0)[0, 0].item())
+                raise ValueError("DTWAligner: pair %d has an empty (all-zero) utterance or could not be aligned" % bad)
+            T_out = max(int(longer.shape[1]), int(longest))     # :55-71 (outputs only ever grow)
+            Xa = _hip.gather_path(Xd, path_i, path_len, T_out).to(longer.dtype)   # :52-54,72
+            Ya = _hip.gather_path(Yd, path_j, path_len, T_out).to(longer.dtype)   # :73
+            if self.verbose > 0:
+                d = (cost / (lenx + leny)).tolist()             # :51
+                for idx in range(N):
+                    print("{}, distance: {}".format(idx, d[idx]))
+        return Xa, Ya
+
     def transform(self, XY):
         X, Y = XY
+        if not isinstance(X, np.ndarray) or not isinstance(Y, np.ndarray):
+            torch = _hip.torch_mod()
+            if torch.is_tensor(X) or torch.is_tensor(Y):
+                return self._transform_tensors(X, Y)
         assert X.ndim == 3 and Y.ndim == 3                 # alignment.py:42
         longer = X if X.shape[1] > Y.shape[1] else Y       # :44
         N = X.shape[0]
         if N == 0:
+            self.path_lengths_ = np.zeros(0, dtype=np.int32)
             return np.zeros_like(longer), np.zeros_like(longer)
         path_i, path_j, plen, cost, lenx, leny, gather = self._paths(X, Y)
+        self.path_lengths_ = np.asarray(plen, dtype=np.int32)
         if (plen <= 0).any():
             bad = int(np.flatnonzero(plen <= 0)[0])
             raise ValueError("DTWAligner: pair %d has an empty (all-zero) utterance or could not be aligned" % bad)

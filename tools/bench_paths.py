@@ -68,6 +68,11 @@
         built-in segment length, 16384, 65536 and unsplit) against torch's plain copy of the same bytes, the same result composed
         from torch operations, and the per-utterance host loop through the reference's expressions (scaled); protocol as f0;
         also written to profiles/wave.json (NNMNKWII_WAVE_PROFILE names another file)
+  joint : (only with --only joint) the joint rows of 512 aligned pairs, Tmax = 2000, lengths in [1000, 2000], 60-dim float32 with
+        column 0 dropped, static + delta + delta-delta, float64 rows (W = 354), about 5 % silent frames: nnmk_joint_count and
+        nnmk_joint_write together and apart, the LIVE keep rule, the same rows composed from delta_features and torch operations,
+        torch's plain copy of the rows the write stage stores, and the reference-style per-utterance host loop (scaled); protocol
+        as f0; also written to profiles/joint.json (NNMNKWII_JOINT_PROFILE names another file)
 
 Each line carries the GPU time (HIP events on the launch stream), the algorithmic bytes, GB/s, and a
 bounded CPU baseline from the oracle on the same host (the checker, timed like bench.py's cpu_baseline).
@@ -1496,6 +1501,132 @@ def _run(only, quick, device_index):
         emit(**res)
         if not args.quick:
             out_path = os.environ.get("NNMNKWII_F0_PROFILE") or os.path.join(ROOT, "profiles", "f0.json")
+            with open(out_path, "w") as fh:
+                json.dump(res, fh, indent=1, sort_keys=True)
+                fh.write("\n")
+
+    # ---- joint: aligned pairs to the rows a joint GMM is fitted on (deltas, concatenation, zero frames out); only with --only joint ----
+    if args.only and "joint" in args.only.split(","):
+        from nnmnkwii_amd import _joint_hip as JH
+        from nnmnkwii_amd import preprocessing as PP
+        B, Tlo, Thi, D0 = (32, 1000, 2000, 60) if args.quick else (512, 1000, 2000, 60)
+        rng = np.random.RandomState(1234)
+        Tmax = Thi
+        lens_h = rng.randint(Tlo, Thi + 1, size=B).astype(np.int32)
+        host_X, host_Y = rng.randn(B, Tmax, D0).astype(np.float32), rng.randn(B, Tmax, D0).astype(np.float32)
+        for b in range(B):                                   # silences of about 20 frames in both sides, about 5 % of the frames
+            t = int(rng.geometric(1.0 / 380))
+            while t < Tmax:
+                n = 1 + int(rng.geometric(1.0 / 20))
+                host_X[b, t:t + n] = 0.0
+                host_Y[b, t:t + n] = 0.0
+                t += n + int(rng.geometric(1.0 / 380))
+        live = int(lens_h.sum())
+        zero_share = float(np.mean([np.mean(np.abs(host_X[b, :lens_h[b]]).sum(1) == 0) for b in range(B)]))
+        wins = [(0, 0, np.array([1.0])), (1, 1, np.array([-0.5, 0.0, 0.5])), (1, 1, np.array([1.0, -2.0, 1.0]))]
+        X0, Y0 = torch.from_numpy(host_X).to(dev), torch.from_numpy(host_Y).to(dev)
+        Ld = torch.from_numpy(lens_h).to(dev)
+        xs, ys = X0[:, :, 1:], Y0[:, :, 1:]                  # column 0 dropped: slices, used where they lie
+        W = 2 * (D0 - 1) * 3
+        plan, offsets = JH.count(xs, ys, Ld, Ld, wins, JH.NONZERO, 1e-7, torch.float64)
+        N = int(offsets[-1].item())
+        out = torch.empty((live, W), dtype=torch.float64, device=dev)       # room for the LIVE mode's rows as well
+
+        def windows(fn, reps, n=7):
+            """Milliseconds per call over `n` windows of `reps` back-to-back calls between two events, after a settled warm-up."""
+            gpu_time(fn, steps=3)
+            res_ = []
+            for _ in range(n):
+                a, b_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(reps):
+                    fn()
+                b_.record()
+                torch.cuda.synchronize()
+                res_.append(a.elapsed_time(b_) / reps)
+            return dict(median_ms=float(np.median(res_)), min_ms=float(min(res_)), max_ms=float(max(res_)), reps=reps, windows=n)
+
+        def both():
+            plan.count(JH.NONZERO, 1e-7, offsets)
+            plan.write(out)
+
+        def both_live():
+            plan.count(JH.LIVE, 0.0, offsets)
+            plan.write(out)
+
+        def composed():
+            """The same rows from the package's delta_features and torch operations (float32 until the final cast)."""
+            dx = _hip.delta_features(xs.contiguous(), wins, Ld)
+            dy = _hip.delta_features(ys.contiguous(), wins, Ld)
+            XY = torch.cat((dx, dy), dim=-1).reshape(-1, W)
+            keep = XY.abs().sum(dim=1, dtype=torch.float64) > 1e-7
+            return XY[keep]
+
+        in_bytes = 4.0 * 2 * (D0 - 1) * live
+        res = dict(path="joint-rows", B=B, Tmax=Tmax, D=D0 - 1, W=W, live_frames=live, kept_rows=N, zero_frame_share=zero_share,
+                   hbm_peak_gbs=HBM_PEAK_GBS, tile=JH.TILE, write_bytes=8.0 * W * N, source_bytes=in_bytes)
+        res["count"] = windows(lambda: plan.count(JH.NONZERO, 1e-7, offsets), 20)
+        plan.count(JH.NONZERO, 1e-7, offsets)
+        res["write"] = windows(lambda: plan.write(out), 10)
+        res["count_and_write"] = windows(both, 10)
+        res["live_count_and_write"] = windows(both_live, 10)
+        res["live_rows"] = int(offsets[-1].item())
+        res["live_count"] = windows(lambda: plan.count(JH.LIVE, 0.0, offsets), 20)
+        both()
+        torch.cuda.synchronize()
+        res["write_hbm_frac"] = (res["write_bytes"] + in_bytes) / (res["write"]["median_ms"] * 1e6) / HBM_PEAK_GBS
+        res["one_call_wall_ms"] = wall_time(lambda: PP.joint_features_batch(xs, ys, Ld, wins), steps=10, warmup=2)
+        # floors: torch's plain copy of the rows the write stage must store, from float64 rows and from float32 rows (a conversion)
+        src64 = torch.empty((N, W), dtype=torch.float64, device=dev).normal_(generator=gen)
+        res["plain_copy_f64"] = windows(lambda: out[:N].copy_(src64), 10)
+        src32 = src64.to(torch.float32)
+        del src64
+        res["plain_convert_f32_to_f64"] = windows(lambda: out[:N].copy_(src32), 10)
+        del src32
+        res["write_over_plain_copy"] = res["write"]["median_ms"] / res["plain_copy_f64"]["median_ms"]
+        res["write_over_plain_convert"] = res["write"]["median_ms"] / res["plain_convert_f32_to_f64"]["median_ms"]
+        del out
+        torch.cuda.empty_cache()
+        res["composed"] = windows(lambda: composed().to(torch.float64), 3, n=5)
+        res["composed_over_count_and_write"] = res["composed"]["median_ms"] / res["count_and_write"]["median_ms"]
+        got32 = PP.joint_features_batch(xs, ys, Ld, wins, dtype=torch.float32)
+        want32 = composed()
+        res["equal_to_composed_float32"] = bool(got32.shape == want32.shape and torch.equal(got32, want32))
+        del got32, want32
+        torch.cuda.empty_cache()
+        # the reference-style loop: per utterance on the host, np.correlate per dimension and window, concatenate, remove the zero frames
+        nloop = min(B, 8)
+        t0 = time.perf_counter()
+        host_rows = []
+        for b in range(nloop):
+            n = int(lens_h[b])
+            blocks = []
+            for src in (host_X, host_Y):
+                x = src[b, :n, 1:]
+                blocks.append(np.concatenate([np.stack([np.correlate(x[:, d], w[2], mode="same") for d in range(x.shape[1])], axis=1)
+                                              for w in wins], axis=1))
+            XY = np.concatenate(blocks, axis=1)
+            host_rows.append(XY[np.sum(np.abs(XY), axis=1) > 1e-7])
+        res["host_loop_utterances"] = nloop
+        res["host_loop_ms"] = (time.perf_counter() - t0) * 1e3
+        res["host_loop_scaled_ms"] = res["host_loop_ms"] * B / nloop
+        got = PP.joint_features_batch(xs[:nloop], ys[:nloop], Ld[:nloop], wins).cpu().numpy()
+        host_rows = np.concatenate(host_rows, axis=0)
+        res["host_loop_equal"] = bool(got.shape == host_rows.shape and np.array_equal(got, host_rows))
+        res["note"] = ("float32 (B, 2000, 60) aligned pairs with column 0 dropped by slicing, lengths 1000 .. 2000, silences of about 20 "
+                       "frames in both sides; static + delta + delta-delta, float64 rows of 354 columns.  count: the mask kernel plus the "
+                       "one-workgroup scan; write: the third stage alone on a counted workspace; count_and_write: the three launches; "
+                       "live_*: the LIVE keep rule (masks from the lengths).  Milliseconds per call between two HIP events around `reps` "
+                       "back-to-back calls, median, least and most of `windows` such windows on settled clocks.  plain_copy_f64 / "
+                       "plain_convert_f32_to_f64: torch's copy_ of (kept_rows, 354) float64 / float32 rows into the same output, the "
+                       "stores the write stage must make with twice / once its row bytes read on top and no computation.  composed: "
+                       "the same rows from two delta_features launches on contiguous copies of the slices, cat, abs-sum in float64, "
+                       "boolean indexing and the cast to float64; equal_to_composed_float32: torch.equal of float32 rows.  host_loop: "
+                       "per utterance np.correlate per dimension and window, concatenate, remove the zero frames, on the first "
+                       "utterances, scaled to the batch.  No counters were collected; no time is asserted anywhere")
+        emit(**res)
+        if not args.quick:
+            out_path = os.environ.get("NNMNKWII_JOINT_PROFILE") or os.path.join(ROOT, "profiles", "joint.json")
             with open(out_path, "w") as fh:
                 json.dump(res, fh, indent=1, sort_keys=True)
                 fh.write("\n")
