@@ -22,11 +22,14 @@ behind the Python signatures of r9y9/nnmnkwii's hot path.
                                 voice-conversion recipe: deltas, concatenation and zero-frame removal in three launches; also exported
                                 from nnmnkwii_amd.preprocessing)
     nnmnkwii_amd.frontend.merlin  frame_features, frame_features_batch (phone-level linguistic features and durations to the
-                                frame-level input matrix of an acoustic model), get_frame_feature_size, coarse_coding_table
+                                frame-level input matrix of an acoustic model), get_frame_feature_size, coarse_coding_table;
+                                kept_frame_features, kept_frame_features_batch (the same without the frames of silent phones)
+    nnmnkwii_amd.preprocessing.silence  remove_silence_frames, remove_silence_frames_batch (the frames of silent phones dropped
+                                from any frame-level matrix over padded batches; also exported from nnmnkwii_amd.preprocessing)
 
 Everything numerical runs in hand-written HIP kernels (``csrc/``) behind the
 C ABI of ``include/mlpg_hip.h`` (the objective metrics: its extension header
-``include/nnmnkwii_metrics.h``; the frontend: ``include/nnmnkwii_frontend.h``; continuous F0: ``include/nnmnkwii_f0.h``; the waveform codec: ``include/nnmnkwii_wave.h``; the joint rows: ``include/nnmnkwii_joint.h``).  There is no CPU fallback: without the built
+``include/nnmnkwii_metrics.h``; the frontend: ``include/nnmnkwii_frontend.h``; continuous F0: ``include/nnmnkwii_f0.h``; the waveform codec: ``include/nnmnkwii_wave.h``; the joint rows: ``include/nnmnkwii_joint.h``; silence removal: ``include/nnmnkwii_silence.h``).  There is no CPU fallback: without the built
 extension or without a GPU the calls raise ``HipExtensionError``.
 """
 from ._hip import HipExtensionError  # noqa: F401

@@ -21,6 +21,7 @@ or a GPU the functions raise ``HipExtensionError``.  CUDA tensors are used where
 import numpy as np
 
 from .. import _frontend_hip as FH
+from .. import _silence_hip as SH
 
 _CC_DEVICE = {}     # device index -> the coarse-coding table on that device
 
@@ -117,6 +118,19 @@ def _validate(phone_features, durations, num_phones, subphone_features, min_fram
     return kind, mf, odt
 
 
+def _validate_silence(silence, durations, who, ndim):
+    """The flags: one bool or integer per phone."""
+    if _is_tensor(silence):
+        shape, ok = tuple(silence.shape), not (silence.dtype.is_floating_point or silence.dtype.is_complex)
+    else:
+        silence = np.asarray(silence)
+        shape, ok = silence.shape, silence.dtype.kind in "biu"
+    want = tuple(durations.shape[:-1])
+    if not ok or shape != want:
+        raise ValueError("%s: silence must hold one bool or integer flag per phone, %s, got shape %s"
+                         % (who, "(N,)" if ndim == 2 else "(B, Nmax)", shape))
+
+
 def _to_device(a, dev, torch, dtype=None):
     if a is None:
         return None
@@ -129,6 +143,48 @@ def _cc_on(dev, torch):
     if t is None:
         t = _CC_DEVICE[dev.index] = torch.from_numpy(coarse_coding_table()).to(dev)
     return t
+
+
+def _batch(who, phone_features, durations, num_phones, subphone_features, silence, min_frames, scale_, min_, Tmax, out, dtype, strict):
+    """frame_features_batch (silence None) and kept_frame_features_batch: validation, placement, the counts where they are
+    needed, one launch."""
+    kind, mf, odt = _validate(phone_features, durations, num_phones, subphone_features, min_frames, scale_, min_, Tmax, out, dtype, who, 3)
+    if silence is not None:
+        _validate_silence(silence, durations, who, 3)
+    from .. import _hip
+    as_tensor = _is_tensor(phone_features)
+    on_device = as_tensor and phone_features.is_cuda
+    dev = _hip.require_gpu(phone_features.device if on_device else (out.device if out is not None else None))
+    torch = _hip.torch_mod()
+    P = _to_device(phone_features, dev, torch)
+    if _is_tensor(durations):
+        d = durations if durations.dtype in (torch.int32, torch.int64, torch.float32, torch.float64) else durations.to(torch.int64)
+    else:
+        d = np.ascontiguousarray(durations)
+        d = torch.from_numpy(d if d.dtype in (np.int32, np.int64, np.float32, np.float64) else d.astype(np.int64))
+    d = d.to(dev).contiguous()
+    sil = None if silence is None else (_to_device(silence if _is_tensor(silence) else np.asarray(silence) != 0, dev, torch) != 0).contiguous()
+    n = _to_device(num_phones if num_phones is None or _is_tensor(num_phones) else np.asarray(num_phones), dev, torch, torch.int32)
+    sc, mn = _to_device(scale_, dev, torch, torch.float64), _to_device(min_, dev, torch, torch.float64)
+    B, W = P.shape[0], P.shape[2] + FH.SIZES[kind]
+    T = out.shape[1] if out is not None else Tmax
+    if T is None or strict:
+        counts = (FH.frame_counts(d, n, mf) if sil is None else SH.frame_counts(d, n, sil, mf)[:, 0]).cpu().numpy()
+        if T is None:
+            T = int(counts.max()) if B else 0
+        elif (counts > int(T)).any():
+            b = int(np.argmax(counts > int(T)))
+            raise ValueError("%s: utterance %d has %d %sframes, Tmax is %d" % (who, b, counts[b], "" if sil is None else "kept ", int(T)))
+    if out is None:
+        out = torch.empty((B, int(T), W), dtype=torch.float32 if odt == np.float32 else torch.float64, device=dev)
+    cc = _cc_on(dev, torch) if kind == FH.COARSE_CODING else None
+    sc, mn = None if sc is None else sc.contiguous(), None if mn is None else mn.contiguous()
+    lengths = FH.expand(P, d, n, kind, mf, cc, sc, mn, out) if sil is None else SH.expand(P, d, n, sil, kind, mf, cc, sc, mn, out)
+    if on_device:
+        return out, lengths
+    if as_tensor:
+        return out.cpu(), lengths.cpu()
+    return out.cpu().numpy(), lengths.cpu().numpy()
 
 
 def frame_features_batch(phone_features, durations, num_phones=None, subphone_features="full", *, min_frames=None, scale_=None, min_=None,
@@ -146,40 +202,8 @@ def frame_features_batch(phone_features, durations, num_phones=None, subphone_fe
     one is given, ``strict=True`` reads the counts back too and raises ``ValueError`` naming the first utterance that does not
     fit; ``strict=False`` synchronises nothing (for stream capture) and truncation shows only in ``lengths``, which are then
     ``Tmax``."""
-    who = "frame_features_batch"
-    kind, mf, odt = _validate(phone_features, durations, num_phones, subphone_features, min_frames, scale_, min_, Tmax, out, dtype, who, 3)
-    from .. import _hip
-    as_tensor = _is_tensor(phone_features)
-    on_device = as_tensor and phone_features.is_cuda
-    dev = _hip.require_gpu(phone_features.device if on_device else (out.device if out is not None else None))
-    torch = _hip.torch_mod()
-    P = _to_device(phone_features, dev, torch)
-    if _is_tensor(durations):
-        d = durations if durations.dtype in (torch.int32, torch.int64, torch.float32, torch.float64) else durations.to(torch.int64)
-    else:
-        d = np.ascontiguousarray(durations)
-        d = torch.from_numpy(d if d.dtype in (np.int32, np.int64, np.float32, np.float64) else d.astype(np.int64))
-    d = d.to(dev).contiguous()
-    n = _to_device(num_phones if num_phones is None or _is_tensor(num_phones) else np.asarray(num_phones), dev, torch, torch.int32)
-    sc, mn = _to_device(scale_, dev, torch, torch.float64), _to_device(min_, dev, torch, torch.float64)
-    B, W = P.shape[0], P.shape[2] + FH.SIZES[kind]
-    T = out.shape[1] if out is not None else Tmax
-    if T is None or strict:
-        counts = FH.frame_counts(d, n, mf).cpu().numpy()
-        if T is None:
-            T = int(counts.max()) if B else 0
-        elif (counts > int(T)).any():
-            b = int(np.argmax(counts > int(T)))
-            raise ValueError("%s: utterance %d has %d frames, Tmax is %d" % (who, b, counts[b], int(T)))
-    if out is None:
-        out = torch.empty((B, int(T), W), dtype=torch.float32 if odt == np.float32 else torch.float64, device=dev)
-    lengths = FH.expand(P, d, n, kind, mf, _cc_on(dev, torch) if kind == FH.COARSE_CODING else None,
-                        None if sc is None else sc.contiguous(), None if mn is None else mn.contiguous(), out)
-    if on_device:
-        return out, lengths
-    if as_tensor:
-        return out.cpu(), lengths.cpu()
-    return out.cpu().numpy(), lengths.cpu().numpy()
+    return _batch("frame_features_batch", phone_features, durations, num_phones, subphone_features, None, min_frames, scale_, min_, Tmax, out,
+                  dtype, strict)
 
 
 def frame_features(phone_features, durations, subphone_features="full", *, min_frames=None, scale_=None, min_=None, dtype=None):
@@ -190,4 +214,39 @@ def frame_features(phone_features, durations, subphone_features="full", *, min_f
     _validate(phone_features, durations, None, subphone_features, min_frames, scale_, min_, None, None, dtype, "frame_features", 2)
     out, _ = frame_features_batch(phone_features[None], durations[None], None, subphone_features, min_frames=min_frames, scale_=scale_, min_=min_,
                                   dtype=dtype)
+    return out[0]
+
+
+def kept_frame_features_batch(phone_features, durations, silence, num_phones=None, subphone_features="full", *, min_frames=None, scale_=None,
+                              min_=None, Tmax=None, out=None, dtype=None, strict=True):
+    """:func:`frame_features_batch` without the frames of silent phones, in one launch: the reference's
+
+        X = linguistic_features(labels, binary_dict, numeric_dict, add_frame_features=True, subphone_features=...)
+        X = np.delete(X, labels.silence_frame_indices(regex), axis=0)
+
+    for every utterance of a padded batch (include/nnmnkwii_silence.h, csrc/frame_keep.hip).  The regular
+    expression is text processing and gives one flag per phone, computed once, anywhere:
+
+        sil = np.zeros(N, bool); sil[labels.silence_phone_indices(regex)] = True
+
+    silence ``(B, Nmax)``: bool or integers, non-zero: the phone is silent and none of its frames is written (or computed).  The
+    sub-phone columns of the kept frames come from their places in the original phones.  Everything else is
+    :func:`frame_features_batch`'s, with ``K_b`` -- the frames of utterance ``b`` whose phone is not flagged -- in the place of
+    ``T_b``: out ``(B, Tmax, Dl + F)`` has zeros behind each utterance's ``K_b`` kept rows, lengths are ``min(K_b, Tmax)``,
+    ``Tmax=None`` reads the largest ``K_b`` back, and ``strict=True`` raises ``ValueError`` naming the first utterance whose
+    kept frames do not fit.  Flags at or past ``num_phones[b]`` are not read."""
+    return _batch("kept_frame_features_batch", phone_features, durations, num_phones, subphone_features, silence, min_frames, scale_, min_, Tmax,
+                  out, dtype, strict)
+
+
+def kept_frame_features(phone_features, durations, silence, subphone_features="full", *, min_frames=None, scale_=None, min_=None, dtype=None):
+    """One utterance: :func:`frame_features` without the frames of the phones flagged in silence ``(N,)`` -- ``(K, Dl + F)``, what
+    ``np.delete(linguistic_features(..., add_frame_features=True), labels.silence_frame_indices(regex), axis=0)`` returns for
+    labels with these durations and ``sil = np.zeros(N, bool); sil[labels.silence_phone_indices(regex)] = True``."""
+    who = "kept_frame_features"
+    _validate(phone_features, durations, None, subphone_features, min_frames, scale_, min_, None, None, dtype, who, 2)
+    _validate_silence(silence, durations, who, 2)
+    silence = silence if _is_tensor(silence) else np.asarray(silence)
+    out, _ = kept_frame_features_batch(phone_features[None], durations[None], silence[None], None, subphone_features, min_frames=min_frames,
+                                       scale_=scale_, min_=min_, dtype=dtype)
     return out[0]
