@@ -62,19 +62,51 @@ def _dur_dtype(t):
         raise ValueError("frontend: durations must be int32, int64, float32 or float64, got %s" % t.dtype)
 
 
-def _check_batch(durations, num_phones):
+def _check_batch(durations, num_phones, who="frontend"):
     torch = _hip.torch_mod()
     if not (torch.is_tensor(durations) and durations.is_cuda and durations.dim() == 3 and durations.is_contiguous()):
-        raise ValueError("frontend: durations must be a contiguous (B, Nmax, S) CUDA tensor")
+        raise ValueError("%s: durations must be a contiguous (B, Nmax, S) CUDA tensor" % who)
     B, Nmax, S = durations.shape
     if not 1 <= S <= MAX_S:
-        raise ValueError("frontend: S must be in 1 .. %d, got %d" % (MAX_S, S))
+        raise ValueError("%s: S must be in 1 .. %d, got %d" % (who, MAX_S, S))
     if Nmax * S > MAX_STATES:
-        raise ValueError("frontend: Nmax * S = %d states, at most %d fit" % (Nmax * S, MAX_STATES))
+        raise ValueError("%s: Nmax * S = %d states, at most %d fit" % (who, Nmax * S, MAX_STATES))
     if num_phones is not None and not (torch.is_tensor(num_phones) and num_phones.dtype == torch.int32 and tuple(num_phones.shape) == (B,)
                                        and num_phones.device == durations.device and num_phones.is_contiguous()):
-        raise ValueError("frontend: num_phones must be an int32 (B) tensor on the durations' device")
+        raise ValueError("%s: num_phones must be an int32 (B) tensor on the durations' device" % who)
     return B, Nmax, S
+
+
+def _min_frames(who, min_frames):
+    if int(min_frames) < 0:
+        raise ValueError("%s: min_frames must be at least 0, got %d" % (who, min_frames))
+    return int(min_frames)
+
+
+def _check_expand(who, cap, B, Nmax, dev, *, phone, kind, min_frames, cc, scale_, min_, out):
+    """The tensor checks that both expansions share (who: "frontend" / "silence", cap: what the caller calls out's rows, "Tmax" /
+    "Tcap"); the tensors go in by keyword.  Returns Dl, the width Dl + F, out's rows and min_frames as an int."""
+    torch = _hip.torch_mod()
+    if not 0 <= int(kind) < len(SIZES):
+        raise ValueError("%s: unknown kind %r" % (who, kind))
+    F = SIZES[kind]
+    if not (torch.is_tensor(phone) and phone.dim() == 3 and tuple(phone.shape[:2]) == (B, Nmax) and phone.device == dev
+            and phone.dtype in (torch.float32, torch.float64)):
+        raise ValueError("%s: phone features must be a float32 / float64 (B, Nmax, Dl) tensor on the durations' device" % who)
+    Dl = phone.shape[2]
+    W = Dl + F
+    if not (torch.is_tensor(out) and out.dim() == 3 and out.shape[0] == B and out.shape[2] == W and out.device == dev
+            and out.dtype in (torch.float32, torch.float64)):
+        raise ValueError("%s: out must be a float32 / float64 (B, %s, %d) tensor on the durations' device" % (who, cap, W))
+    for name, t in (("scale_", scale_), ("min_", min_)):
+        if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float64 and tuple(t.shape) == (W,) and t.device == dev and t.is_contiguous()):
+            raise ValueError("%s: %s must be a float64 (%d) tensor on the durations' device" % (who, name, W))
+    if (scale_ is None) != (min_ is None):
+        raise ValueError("%s: scale_ and min_ go together" % who)
+    if kind == COARSE_CODING and not (torch.is_tensor(cc) and cc.dtype == torch.float64 and tuple(cc.shape) == (3, CC_POINTS) and cc.device == dev
+                                      and cc.is_contiguous()):
+        raise ValueError("%s: the coarse-coding kind needs its float64 (3, %d) table on the durations' device" % (who, CC_POINTS))
+    return Dl, W, out.shape[1], _min_frames(who, min_frames)
 
 
 def frame_counts(durations, num_phones=None, min_frames=0):
@@ -82,13 +114,12 @@ def frame_counts(durations, num_phones=None, min_frames=0):
     int32 (B) or None.  Returns the frames of every utterance, int64 (B) on the device.  One launch, no synchronisation."""
     B, Nmax, S = _check_batch(durations, num_phones)
     dt = _dur_dtype(durations)
-    if int(min_frames) < 0:
-        raise ValueError("frontend: min_frames must be at least 0, got %d" % min_frames)
+    mf = _min_frames("frontend", min_frames)
     torch = _hip.torch_mod()
     L = lib()
     dev = durations.device
     counts = torch.empty((B,), dtype=torch.int64, device=dev)
-    rc = L.nnmk_frontend_frame_counts(dev.index, _hip._stream(dev), dt, _hip._p(durations), _hip._p(num_phones), B, Nmax, S, int(min_frames),
+    rc = L.nnmk_frontend_frame_counts(dev.index, _hip._stream(dev), dt, _hip._p(durations), _hip._p(num_phones), B, Nmax, S, mf,
                                       _hip._p(counts))
     _hip._check(rc, "nnmk_frontend_frame_counts")
     return counts
@@ -104,35 +135,15 @@ def expand(phone, durations, num_phones, kind, min_frames, cc, scale_, min_, out
     B, Nmax, S = _check_batch(durations, num_phones)
     dt = _dur_dtype(durations)
     dev = durations.device
-    if not 0 <= int(kind) < len(SIZES):
-        raise ValueError("frontend: unknown kind %r" % (kind,))
-    F = SIZES[kind]
-    if not (torch.is_tensor(phone) and phone.dim() == 3 and tuple(phone.shape[:2]) == (B, Nmax) and phone.device == dev
-            and phone.dtype in (torch.float32, torch.float64)):
-        raise ValueError("frontend: phone features must be a float32 / float64 (B, Nmax, Dl) tensor on the durations' device")
-    Dl = phone.shape[2]
-    W = Dl + F
-    if not (torch.is_tensor(out) and out.dim() == 3 and out.shape[0] == B and out.shape[2] == W and out.device == dev
-            and out.dtype in (torch.float32, torch.float64)):
-        raise ValueError("frontend: out must be a float32 / float64 (B, Tmax, %d) tensor on the durations' device" % W)
-    Tmax = out.shape[1]
-    for name, t in (("scale_", scale_), ("min_", min_)):
-        if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float64 and tuple(t.shape) == (W,) and t.device == dev and t.is_contiguous()):
-            raise ValueError("frontend: %s must be a float64 (%d) tensor on the durations' device" % (name, W))
-    if (scale_ is None) != (min_ is None):
-        raise ValueError("frontend: scale_ and min_ go together")
-    if kind == COARSE_CODING and not (torch.is_tensor(cc) and cc.dtype == torch.float64 and tuple(cc.shape) == (3, CC_POINTS) and cc.device == dev
-                                      and cc.is_contiguous()):
-        raise ValueError("frontend: the coarse-coding kind needs its float64 (3, %d) table on the durations' device" % CC_POINTS)
-    if int(min_frames) < 0:
-        raise ValueError("frontend: min_frames must be at least 0, got %d" % min_frames)
+    Dl, W, Tmax, mf = _check_expand("frontend", "Tmax", B, Nmax, dev, phone=phone, kind=kind, min_frames=min_frames, cc=cc, scale_=scale_,
+                                    min_=min_, out=out)
     L = lib()
     ld_p = _hip._pf_row_stride(phone, B, Nmax, Dl, "frontend") if Dl else 0
     ld_out = _hip._pf_row_stride(out, B, Tmax, W, "frontend") if W else 0
     if lengths_out is None:
         lengths_out = torch.empty((B,), dtype=torch.int32, device=dev)
     rc = L.nnmk_frontend_expand(dev.index, _hip._stream(dev), _hip._dt(phone), _hip._p(phone), ld_p, dt, _hip._p(durations), _hip._p(num_phones),
-                                B, Nmax, S, Dl, int(min_frames), int(kind), _hip._p(cc) if kind == COARSE_CODING else None, _hip._p(scale_),
+                                B, Nmax, S, Dl, mf, int(kind), _hip._p(cc) if kind == COARSE_CODING else None, _hip._p(scale_),
                                 _hip._p(min_), _hip._dt(out), _hip._p(out), ld_out, Tmax, _hip._p(lengths_out))
     _hip._check(rc, "nnmk_frontend_expand")
     return lengths_out

@@ -49,26 +49,11 @@ def lib():
 
 def _check_batch(durations, num_phones, silence):
     torch = _hip.torch_mod()
-    if not (torch.is_tensor(durations) and durations.is_cuda and durations.dim() == 3 and durations.is_contiguous()):
-        raise ValueError("silence: durations must be a contiguous (B, Nmax, S) CUDA tensor")
-    B, Nmax, S = durations.shape
-    if not 1 <= S <= FH.MAX_S:
-        raise ValueError("silence: S must be in 1 .. %d, got %d" % (FH.MAX_S, S))
-    if Nmax * S > FH.MAX_STATES:
-        raise ValueError("silence: Nmax * S = %d states, at most %d fit" % (Nmax * S, FH.MAX_STATES))
-    if num_phones is not None and not (torch.is_tensor(num_phones) and num_phones.dtype == torch.int32 and tuple(num_phones.shape) == (B,)
-                                       and num_phones.device == durations.device and num_phones.is_contiguous()):
-        raise ValueError("silence: num_phones must be an int32 (B) tensor on the durations' device")
+    B, Nmax, S = FH._check_batch(durations, num_phones, "silence")
     if not (torch.is_tensor(silence) and silence.dtype in (torch.bool, torch.uint8) and tuple(silence.shape) == (B, Nmax)
             and silence.device == durations.device and silence.is_contiguous()):
         raise ValueError("silence: the flags must be a contiguous bool / uint8 (B, Nmax) tensor on the durations' device")
     return B, Nmax, S
-
-
-def _min_frames(min_frames):
-    if int(min_frames) < 0:
-        raise ValueError("silence: min_frames must be at least 0, got %d" % min_frames)
-    return int(min_frames)
 
 
 def frame_counts(durations, num_phones, silence, min_frames=0):
@@ -77,7 +62,7 @@ def frame_counts(durations, num_phones, silence, min_frames=0):
     T_b of every utterance.  One launch, no synchronisation."""
     B, Nmax, S = _check_batch(durations, num_phones, silence)
     dt = FH._dur_dtype(durations)
-    mf = _min_frames(min_frames)
+    mf = FH._min_frames("silence", min_frames)
     torch = _hip.torch_mod()
     L = lib()
     dev = durations.device
@@ -95,27 +80,8 @@ def expand(phone, durations, num_phones, silence, kind, min_frames, cc, scale_, 
     B, Nmax, S = _check_batch(durations, num_phones, silence)
     dt = FH._dur_dtype(durations)
     dev = durations.device
-    if not 0 <= int(kind) < len(FH.SIZES):
-        raise ValueError("silence: unknown kind %r" % (kind,))
-    F = FH.SIZES[kind]
-    if not (torch.is_tensor(phone) and phone.dim() == 3 and tuple(phone.shape[:2]) == (B, Nmax) and phone.device == dev
-            and phone.dtype in (torch.float32, torch.float64)):
-        raise ValueError("silence: phone features must be a float32 / float64 (B, Nmax, Dl) tensor on the durations' device")
-    Dl = phone.shape[2]
-    W = Dl + F
-    if not (torch.is_tensor(out) and out.dim() == 3 and out.shape[0] == B and out.shape[2] == W and out.device == dev
-            and out.dtype in (torch.float32, torch.float64)):
-        raise ValueError("silence: out must be a float32 / float64 (B, Tcap, %d) tensor on the durations' device" % W)
-    Tcap = out.shape[1]
-    for name, t in (("scale_", scale_), ("min_", min_)):
-        if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float64 and tuple(t.shape) == (W,) and t.device == dev and t.is_contiguous()):
-            raise ValueError("silence: %s must be a float64 (%d) tensor on the durations' device" % (name, W))
-    if (scale_ is None) != (min_ is None):
-        raise ValueError("silence: scale_ and min_ go together")
-    if kind == FH.COARSE_CODING and not (torch.is_tensor(cc) and cc.dtype == torch.float64 and tuple(cc.shape) == (3, FH.CC_POINTS)
-                                         and cc.device == dev and cc.is_contiguous()):
-        raise ValueError("silence: the coarse-coding kind needs its float64 (3, %d) table on the durations' device" % FH.CC_POINTS)
-    mf = _min_frames(min_frames)
+    Dl, W, Tcap, mf = FH._check_expand("silence", "Tcap", B, Nmax, dev, phone=phone, kind=kind, min_frames=min_frames, cc=cc, scale_=scale_,
+                                       min_=min_, out=out)
     L = lib()
     ld_p = _hip._pf_row_stride(phone, B, Nmax, Dl, "silence") if Dl else 0
     ld_out = _hip._pf_row_stride(out, B, Tcap, W, "silence") if W else 0
@@ -149,7 +115,7 @@ def gather(src, len_src, durations, num_phones, silence, min_frames, out, length
         raise ValueError("silence: the source's lengths must be an int32 (B) tensor on the durations' device")
     if B * Tcap * D and out.data_ptr() == src.data_ptr():
         raise ValueError("silence: out must not be the source (rows move across workgroups)")
-    mf = _min_frames(min_frames)
+    mf = FH._min_frames("silence", min_frames)
     L = lib()
     ld_src = _hip._pf_row_stride(src, B, Tmax, D, "silence") if D else 0
     ld_out = _hip._pf_row_stride(out, B, Tcap, D, "silence") if D else 0

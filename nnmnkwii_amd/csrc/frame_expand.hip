@@ -28,10 +28,6 @@
 #include "common.h"
 #include "../../include/nnmnkwii_frontend.h"
 
-#ifndef NNMK_FRONTEND_NT_STORES
-#define NNMK_FRONTEND_NT_STORES 0   // 1: nontemporal stores of the output (measured; not the default)
-#endif
-
 namespace mlpg {
 
 namespace {
@@ -135,15 +131,6 @@ __device__ inline void fx_subphone(int kind, const double *__restrict__ cc, int 
   }
 }
 
-template <typename T>
-__device__ inline void fx_store(T *p, T v) {
-#if NNMK_FRONTEND_NT_STORES
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
-
 template <typename TP, typename TO>
 __global__ __launch_bounds__(256) void expand_kernel(FxArgs a) {
   extern __shared__ double fx_lds[];
@@ -233,7 +220,7 @@ __global__ __launch_bounds__(256) void expand_kernel(FxArgs a) {
       const int ph = rowphone[r];
       TO *o = out + (size_t)r * a.ld_out + c;
       if (ph < 0) {
-        fx_store(o, (TO)0);
+        *o = (TO)0;
         continue;
       }
       if (c < Dl) {
@@ -243,11 +230,11 @@ __global__ __launch_bounds__(256) void expand_kernel(FxArgs a) {
           pv = (TO)v;
           prev = ph;
         }
-        fx_store(o, pv);
+        *o = pv;
       } else {
         double v = feat[r * kFxMaxF + (c - Dl)];
         if (affine) v = v * sc + mn;
-        fx_store(o, (TO)v);
+        *o = (TO)v;
       }
     }
   }
