@@ -30,6 +30,18 @@
  *  - Re-entrant per (device, stream); internal scratch is cached per device
  *    and released by mlpg_hip_shutdown().  No OpenMP, no global mutable state
  *    besides that cache and the last-error string (thread-local).
+ *  - Scratch and HIP graphs.  The scratch of a (device, stream) only grows: a
+ *    call that needs more than its slot holds synchronises the stream, frees
+ *    the slot and allocates a larger one.  None of that can happen while the
+ *    stream is being captured, so an entry that uses scratch -- the solve
+ *    routes of mlpg_hip_forward / _backward / _backward_var / _streams,
+ *    mlpg_hip_fastdtw and the dtw_level calls, the direct and chirp-z routes
+ *    of the modspec calls -- is "capturable once that scratch exists": run
+ *    one call of the largest shape on the stream, then capture.  A captured
+ *    graph holds the slot's address.  AFTER A CAPTURE, NO LARGER CALL ON THAT
+ *    STREAM WHILE THE GRAPH LIVES: it would free the slot the graph's kernels
+ *    still write to.  Calls of the same or a smaller shape, replays and calls
+ *    on other streams are fine.
  */
 #ifndef MLPG_HIP_H_
 #define MLPG_HIP_H_
@@ -493,7 +505,9 @@ int mlpg_hip_modspec_route(int n);
  * in one launch that keeps the spectrum in LDS (forward FFT, residual, inverse FFT) plus one small launch that adds the
  * workgroups' partial sums in a fixed order: the loss is the same bit for bit on every call.  `workspace`: at least
  * mlpg_hip_modspec_loss_workspace_bytes(B, D) bytes, 8-byte aligned, owned by the caller, content irrelevant, not to be shared
- * by calls that may overlap.  n_elems is normally B * (n/2+1) * D.  mlpg_hip_modspec_loss_form(n): 1 when the step takes this
+ * by calls that may overlap (the Python wrapper keeps one per (device, stream), allocated on first use and again when a batch
+ * outgrows it: the wrapper's step is not capturable into a graph; the C call allocates nothing).  n_elems is normally
+ * B * (n/2+1) * D.  mlpg_hip_modspec_loss_form(n): 1 when the step takes this
  * n (a power of two in [2, 4096] on the FFT route), 0 when the caller has to compose mlpg_hip_modspec_batch, its own loss
  * and mlpg_hip_modspec_batch_backward (any other n; every n after mlpg_hip_modspec_set_direct(1)).
  */

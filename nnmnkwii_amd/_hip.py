@@ -894,7 +894,9 @@ def _ms_loss_workspace(device, B, D):
 def modspec_loss_step(x, target_ms, n, ortho=False, lengths=None, log_domain=True, eps=1e-10, n_elems=None):
     """Fused modulation-spectrum loss step on device tensors (mlpg_hip_modspec_loss_step): x (B, Tmax, D), target_ms
     (B, n/2+1, D), float32 or float64.  Returns (loss float64 0-dim tensor = sum (f(MS(x)) - f(target_ms))^2 / n_elems,
-    grad_x (B, Tmax, D) = d loss / d x); f = log(. + eps) or the identity.  n must be one modspec_loss_form answers 1 for."""
+    grad_x (B, Tmax, D) = d loss / d x); f = log(. + eps) or the identity.  n must be one modspec_loss_form answers 1 for.
+    Enqueued on the current stream, no synchronisation.  The per-(device, stream) workspace is allocated on first use and again
+    when a batch outgrows it: capturing the step into a graph is not supported."""
     torch = torch_mod()
     B, T, D = _batch_args(x, lengths)
     assert target_ms.shape == (B, n // 2 + 1, D) and target_ms.dtype == x.dtype and target_ms.device == x.device and \
