@@ -14,7 +14,9 @@
 //   level 1 (wavefront, registers): assemble the chunk's rows of P = sum_w W_w^T diag(tau_w) W_w
 //     and b from the frames f0-1 .. f0+16 -- streamed in frame order with a ring of RingDepth<TIN> frames of
 //     loads in flight (assemble_eliminate; window-major assemble + eliminate for window sets other than
-//     three windows) -- and eliminate the 14 interior frames as their rows complete, carrying the
+//     three windows; in the forward float64 standard-window kernel the ring's loads carry a cache policy by frame:
+//     `nt` for the 14 frames only this chunk reads, the default for the 4 its neighbours read too -- row_load_aux)
+//     -- and eliminate the 14 interior frames as their rows complete, carrying the
 //     two "left spike" columns that couple the chunk to the previous chunk's last two frames (its
 //     separator); the elimination runs on into the chunk's own separator -> 14 numbers per lane;
 //   level 2 (workgroup, LDS): the block-tridiagonal system (2x2 blocks) of the strip's W
@@ -102,6 +104,37 @@ constexpr int kEarlyRows = 4;
 // Trajectory and gradient rows go out by buffer stores with the nontemporal hint (written once, never read by this kernel): the
 // cache-policy immediate of those stores.  Round 5 A/B (profiles/r05_strip_stores_ab.txt): forward f64 +1.9 %, backward f32 +5.5 %.
 constexpr int kRowStoreAux = 2;
+// Level 1's row loads (assemble_eliminate): the cache-policy immediate by frame index i of the chunk, -1 .. kM.  A chunk's boundary
+// frames -1, 0, kM-1, kM are read twice -- by this chunk and, 5-8 us apart, by its neighbour: a wavefront of the same workgroup or a
+// workgroup of the same XCD's ticket list, behind the same L2 -- and keep the default policy; the kM-2 frames that nobody else
+// reads carry `nt`, so that the single-use lines are the ones the L2 gives up first.  (`nt` on ALL row loads, round 3: no effect --
+// no line is preferred then.)  What it buys in fetched bytes and in time: profiles/strip_row_policy_notes.md.
+// Which instantiations: row_policy_on.  Only the forward float64 standard-window kernel with per-frame variances gains; with the rule
+// in every instantiation the backward kernels, the transposed form, float32 forward and the merged launches were all slower (the
+// notes, section 4).
+// MLPG_STRIP_ROW_POLICY: 0 policy 0 on every frame (the A side of the notes), 1 the gaining instantiation only.  2 puts the rule into
+// every instantiation: a measurement aid that reproduces section 4 of the notes, slower on most paths and never to be shipped.
+#ifndef MLPG_STRIP_ROW_POLICY
+#define MLPG_STRIP_ROW_POLICY 1
+#endif
+constexpr int row_load_aux(int i) {
+  return MLPG_STRIP_ROW_POLICY && !(i == -1 || i == 0 || i == kM - 1 || i == kM) ? 2 : 0;
+}
+template <typename TIN, bool BWD, int VM, bool MULTI, bool TR, bool STD>
+constexpr bool row_policy_on() {
+  return MLPG_STRIP_ROW_POLICY >= 2 ||
+         (std::is_same<TIN, double>::value && !BWD && VM == MLPG_HIP_VAR_FRAME && !MULTI && !TR && STD);
+}
+template <int I>
+using RowAux = std::integral_constant<int, row_load_aux(I)>;  // frame I's policy as a type: what load_frame takes beside the index
+// assemble_eliminate's prologue loads ring slots sl = 0 .. ring-1 (frame sl-1) in three runs with the policies of frames 0, 1 and kM
+constexpr bool pro_runs_match_rule(int ring) {
+  for (int sl = 0; sl < ring; ++sl) {
+    const int run = sl < 2 ? 0 : (sl < kM ? 1 : kM);
+    if (row_load_aux(sl - 1) != row_load_aux(run)) return false;
+  }
+  return true;
+}
 #ifndef MLPG_STRIP_RING_F64
 #define MLPG_STRIP_RING_F64 6
 #endif
@@ -547,7 +580,8 @@ struct RingDepth<float> { static constexpr int value = MLPG_STRIP_RING_F32; };  
 // and everything wave-uniform go by -- and Tu this lane's own: its dead frames enter with precision 0 and mean 0 by per-lane
 // SELECTS (their values are padding: anything), its rows >= Tu become identity rows.
 // STD: the three standard windows as compile-time coefficients (kStd4; `wc` is not read)
-template <typename TIN, bool BWD, int VM, bool EDGE, int NW, bool MULTI = false, bool LT = false, bool STD = false>
+// POLICY: the row loads carry the per-frame cache policy of row_load_aux (the caller decides by row_policy_on); else policy 0
+template <typename TIN, bool BWD, int VM, bool EDGE, int NW, bool MULTI = false, bool LT = false, bool STD = false, bool POLICY = false>
 __device__ __forceinline__ bool assemble_eliminate(__amdgpu_buffer_rsrc_t mrs, __amdgpu_buffer_rsrc_t vrs,
                                                    __amdgpu_buffer_rsrc_t grs, const TIN *__restrict__ vglob,
                                                    unsigned loff, long ldi, long ldg, int sd, int f0, int T, int mw,
@@ -588,7 +622,9 @@ __device__ __forceinline__ bool assemble_eliminate(__amdgpu_buffer_rsrc_t mrs, _
   // stays until a change to those units is measured on its own.
   float tau_unread[kM + 1][NW];
   TIN rv[kRing][NW], rm[kRing][NW];
-  auto load_frame = [&](TIN (&v)[NW], TIN (&m)[NW], const int i) __attribute__((always_inline)) {
+  auto load_frame = [&](TIN (&v)[NW], TIN (&m)[NW], const int i, auto policy) __attribute__((always_inline)) {
+    // the frame's cache policy (row_load_aux); the EDGE copy clamps its rows at run time -- its frames may all coincide -- and keeps 0
+    constexpr int kAux = (EDGE || !POLICY) ? 0 : decltype(policy)::value;
     // BWD: the frame's row offset as an opaque scalar, so that the 18 multiples i * ldi_bytes (and their EDGE variants) are
     // not hoisted out of the persistent item loop as invariants that occupy scalar registers through the whole kernel.
     // (Part of round 5's hunt for the backward instances' scalar spills; what removed the v_readlane reloads in the stream
@@ -607,8 +643,8 @@ __device__ __forceinline__ bool assemble_eliminate(__amdgpu_buffer_rsrc_t mrs, _
       // lane offset; otherwise it is wave-uniform and rides in the scalar offset
       const unsigned soff = MULTI ? frame_off : frame_off + (unsigned)w * win_bytes;
       const unsigned voff = MULTI ? loff + (unsigned)w * win_bytes : loff;
-      if (VM == MLPG_HIP_VAR_FRAME) v[w] = buf_ld<TIN>(vrs, soff, voff);
-      if (!BWD) m[w] = buf_ld<TIN>(mrs, soff, voff);
+      if (VM == MLPG_HIP_VAR_FRAME) v[w] = buf_ld<TIN, kAux>(vrs, soff, voff);
+      if (!BWD) m[w] = buf_ld<TIN, kAux>(mrs, soff, voff);
     }
   };
   auto accumulate_frame = [&](const TIN (&v)[NW], const TIN (&m)[NW], const int i) __attribute__((always_inline)) {
@@ -762,8 +798,17 @@ __device__ __forceinline__ bool assemble_eliminate(__amdgpu_buffer_rsrc_t mrs, _
   };
 
   // prologue: the first kRing frames (f0-1 ..) in flight
+  // (Loops, not literal calls, and no branch on the policy in a loop's body: either moves every strip unit's register allocation.
+  // The loop index is no constant expression, so the prologue is one plain loop per run of frames with one policy: the head -1, 0,
+  // the interior up to kM-2, and -- only with a ring deeper than the chunk -- the tail.  pro_runs_match_rule holds them to row_load_aux.)
+  constexpr int kProMid = kRing < kM ? kRing : kM;  // slot of frame kM-1, the first of the tail, if the prologue reaches it
 #pragma unroll
-  for (int sl = 0; sl < kRing; ++sl) load_frame(rv[sl], rm[sl], sl - 1);
+  for (int sl = 0; sl < 2; ++sl) load_frame(rv[sl], rm[sl], sl - 1, RowAux<0>{});
+#pragma unroll
+  for (int sl = 2; sl < kProMid; ++sl) load_frame(rv[sl], rm[sl], sl - 1, RowAux<1>{});
+#pragma unroll
+  for (int sl = kProMid; sl < kRing; ++sl) load_frame(rv[sl], rm[sl], sl - 1, RowAux<kM>{});
+  static_assert(pro_runs_match_rule(kRing), "the prologue's three runs of frames must carry the policies of row_load_aux");
   static_assert(kRing >= 2 && kRing <= kM + 2, "ring depth");
   if (BWD) {
 #pragma unroll
@@ -782,7 +827,7 @@ __device__ __forceinline__ bool assemble_eliminate(__amdgpu_buffer_rsrc_t mrs, _
   if ((S) < kM + 2) {                                                                   \
   accumulate_frame(rv[(S) % kRing], rm[(S) % kRing], (S)-1);                            \
   STRIP_SB(1);                                                                          \
-  if ((S) + kRing < kM + 2) { load_frame(rv[(S) % kRing], rm[(S) % kRing], (S)-1 + kRing); } \
+  if ((S) + kRing < kM + 2) { load_frame(rv[(S) % kRing], rm[(S) % kRing], (S)-1 + kRing, RowAux<(S)-1 + kRing>{}); } \
   STRIP_SB(2);                                                                          \
   if ((S)-2 >= 0 && (S)-2 < kN) { elim_row((S)-2); }                                    \
   STRIP_SB(4);                                                                          \
@@ -1064,7 +1109,7 @@ __global__ __launch_bounds__(kW * 64, MLPG_STRIP_WGS) void strip_kernel(Problem 
         karg_f64x9<kKargWc + 2 * 72>(wcl[2]);
         wcs = wcl;
       }
-      if (interior) bad = assemble_eliminate<TIN, BWD, VM, false, 3, MULTI, false, STD>(mrs, vrs, grs, vglob, loff, ldi, ldg, sd, f0, T, mw, wcs, a.one, Pd, P1, P2, rhs, ca, cb, cc, rec);
+      if (interior) bad = assemble_eliminate<TIN, BWD, VM, false, 3, MULTI, false, STD, row_policy_on<TIN, BWD, VM, MULTI, TR, STD>()>(mrs, vrs, grs, vglob, loff, ldi, ldg, sd, f0, T, mw, wcs, a.one, Pd, P1, P2, rhs, ca, cb, cc, rec);
       else bad = assemble_eliminate<TIN, BWD, VM, true, 3, MULTI, TR, STD>(mrs, vrs, grs, vglob, loff, ldi, ldg, sd, f0, T, mw, wcs, a.one, Pd, P1, P2, rhs, ca, cb, cc, rec, Tu);
       STRIP_TICK(1);
 #ifdef MLPG_STRIP_TRACE

@@ -11,9 +11,12 @@ a CU (<= 256 VGPRs, no scratch).
     python tools/strip_isa_stats.py mlpg_strip_bwd_f32.hip mlpg_strip_std_bwd_f32.hip
     python tools/strip_isa_stats.py --json ...
     python tools/strip_isa_stats.py --digest [--csrc DIR] [UNIT ...]   # sha256 of each unit's device assembly (all units if none named)
+    python tools/strip_isa_stats.py --digest-policy-blind --strip-units   # the same, blind to the cache policy of buffer loads
+    python tools/strip_isa_stats.py --digest --strip-units -D MLPG_STRIP_ROW_POLICY=0
 
 --digest is the proof that a refactor left the device code alone: run it on two trees (this one, and another tree's csrc through
---csrc) and compare the two outputs with diff.
+--csrc) and compare the two outputs with diff.  --digest-policy-blind proves the same of a change that may only alter the cache policy
+of row loads (row_load_aux in mlpg_strip_impl.h): the digest is taken after the nt / sc0 / sc1 suffix of buffer_load lines is removed.
 
 tests/test_strip_isa_stats.py pins the standard-window forward-float64 instance against the general one with it.
 """
@@ -50,12 +53,13 @@ def _flags(src):
     return [*B.FLAGS, *B.FILE_FLAGS.get(src, ["-ffp-contract=fast"]), *B.EXTRA]
 
 
-def assembly(src, hipcc=None, csrc=None):
-    """The device-side assembly text of one translation unit of csrc/ (or of another tree's csrc directory)."""
+def assembly(src, hipcc=None, csrc=None, extra=()):
+    """The device-side assembly text of one translation unit of csrc/ (or of another tree's csrc directory); extra: more compiler
+    flags, such as -DMLPG_STRIP_ROW_POLICY=0."""
     hipcc = hipcc or find_hipcc()
     if hipcc is None:
         raise RuntimeError("hipcc not found")
-    cmd = [hipcc, "-x", "hip", *_flags(src), "--cuda-device-only", "-S", os.path.join(csrc or CSRC, src), "-o", "-"]
+    cmd = [hipcc, "-x", "hip", *_flags(src), *extra, "--cuda-device-only", "-S", os.path.join(csrc or CSRC, src), "-o", "-"]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed:\n%s\n%s" % (" ".join(cmd), r.stderr[-4000:]))
@@ -69,11 +73,33 @@ def digest(asm):
     return hashlib.sha256("\n".join(kept).encode()).hexdigest()
 
 
-def digests(sources, csrc=None, jobs=16):
-    """[(unit, digest)] in the order given, compiling at most `jobs` units at a time."""
+_POLICY = re.compile(r"\s+(?:nt|sc0|sc1)\b")
+
+
+def policy_blind(asm):
+    """The assembly text with the cache-policy suffix (nt, sc0, sc1) of every buffer_load line removed: two builds that differ only in
+    the policy of their row loads (MLPG_STRIP_ROW_POLICY) give the same text.  The scope bits sc0 / sc1 go with it, so this text is
+    blind to a changed scope of a buffer load too: its digest proves something only beside the plain --digest of the
+    -DMLPG_STRIP_ROW_POLICY=0 build, which must equal the other tree's."""
+    out = []
+    for line in asm.splitlines():
+        t = line.lstrip()
+        if t.startswith("buffer_load_"):
+            code, sep, comment = line.partition(";")
+            line = _POLICY.sub("", code) + sep + comment
+        out.append(line)
+    return "\n".join(out)
+
+
+def digests(sources, csrc=None, jobs=16, blind=False, extra=()):
+    """[(unit, digest)] in the order given, compiling at most `jobs` units at a time.  blind: of the policy-blind text."""
     from concurrent.futures import ThreadPoolExecutor
+
+    def one(src):
+        asm = assembly(src, csrc=csrc, extra=extra)
+        return digest(policy_blind(asm) if blind else asm)
     with ThreadPoolExecutor(max_workers=max(1, min(jobs, 16))) as ex:
-        return list(zip(sources, ex.map(lambda src: digest(assembly(src, csrc=csrc)), sources)))
+        return list(zip(sources, ex.map(one, sources)))
 
 
 def _classify(op):
@@ -174,6 +200,10 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("sources", nargs="*", help="translation units of nnmnkwii_amd/csrc (default: %s; --digest: all of build.SOURCES)" % " ".join(DEFAULT))
     ap.add_argument("--digest", action="store_true", help="one line 'sha256  unit' per unit: the device assembly without its __hip_cuid_ lines")
+    ap.add_argument("--digest-policy-blind", action="store_true",
+                    help="as --digest, of the text without the cache-policy suffix (nt, sc0, sc1) of its buffer_load lines")
+    ap.add_argument("--strip-units", action="store_true", help="--digest: the mlpg_strip*.hip units of build.SOURCES instead of all")
+    ap.add_argument("-D", dest="defines", action="append", default=[], metavar="NAME=VALUE", help="a macro for the compiler (repeatable)")
     ap.add_argument("--csrc", metavar="DIR", help="compile the units of this csrc directory (another tree's) with this tree's flags")
     ap.add_argument("--jobs", type=int, default=min(16, os.cpu_count() or 1), help="--digest: units compiled at a time (at most 16)")
     ap.add_argument("--json", action="store_true", help="one JSON object instead of the table")
@@ -183,11 +213,12 @@ def main():
         print("hipcc not found", file=sys.stderr)
         return 2
     csrc = os.path.abspath(args.csrc) if args.csrc else None
-    if args.digest:
+    extra = ["-D" + d for d in args.defines]
+    if args.digest or args.digest_policy_blind:
         if not args.sources:
             _flags("")  # (imports build)
-            args.sources = list(sys.modules["nnmnkwii_amd.csrc.build"].SOURCES)
-        for src, dg in digests([os.path.basename(s) for s in args.sources], csrc, args.jobs):
+            args.sources = [s for s in sys.modules["nnmnkwii_amd.csrc.build"].SOURCES if not args.strip_units or s.startswith("mlpg_strip")]
+        for src, dg in digests([os.path.basename(s) for s in args.sources], csrc, args.jobs, blind=args.digest_policy_blind, extra=extra):
             print("%s  %s" % (dg, src))
         return 0
     res = {}
