@@ -23,6 +23,9 @@ __all__ = [
     "gv_stats",
     "mlpg_gv",
     "mlpg_gv_batch",
+    "mlpg_covariance_batch",
+    "mlpg_variance",
+    "mlpg_logdet",
 ]
 
 
@@ -438,6 +441,83 @@ def mlpg_gv(mean_frames, variance_frames, windows, gv_mean, gv_var, n_iter=100, 
         variance_frames = variance_frames[None]
     y = mlpg_gv_batch(mean_frames[None], variance_frames, windows, gv_mean, gv_var, None, n_iter, step, init, omega_scale)
     return y[0].astype(dtype, copy=False)
+
+
+# ---- the covariance of the trajectory distribution N(c; cbar, R^-1) ------------------------------------------------
+def raise_on_trajectory_status(status):
+    """The reference's LinAlgError for the first (utterance, dim) whose R has a non-positive pivot; the frame is the minor."""
+    st = status.cpu().numpy() if hasattr(status, "cpu") else np.asarray(status)
+    bad = np.argwhere(st != 0)
+    if len(bad):
+        b, d = (int(i) for i in bad[0])
+        raise np.linalg.LinAlgError("%d-th leading minor not positive definite (utterance %d, dim %d, frame %d)"
+                                    % (int(st[b, d]), b, d, int(st[b, d]) - 1))
+
+
+def mlpg_covariance_batch(variances, windows, lengths=None, *, B=None, Tmax=None, band=True, out=None):
+    """The other half of MLPG's trajectory distribution ``N(c; cbar, R^-1)`` over a zero-padded batch: the band of the covariance
+    ``S = R^-1`` and ``log det R`` of every (utterance, static dim), ``R = sum_w W_w' diag(1 / var_w) W_w`` with the reference's
+    edge-frame and dtype rules -- the matrix every ``mlpg`` route solves with.  One launch of ``nnmk_traj_covariance``: banded
+    ``L D L'`` and Takahashi's recurrence, ``O(T Q^2)`` per system, no dense ``T x T`` matrix anywhere.
+
+    ``variances``: ``(B, Tmax, D)``, a global ``(D,)`` or ``None`` (unit variances: one static dim), numpy or CUDA tensors,
+    float32 or float64; ``(D,)`` and ``None`` are read in place, never broadcast to a copy, and take the batch shape from
+    ``lengths`` / ``B`` / ``Tmax``.  Returns ``(band, logdet)``, float64, the kind of ``variances`` (numpy unless a CUDA tensor was
+    given): ``band`` ``(Q + 1, B, Tmax, static_dim)`` with ``band[k, b, t] = S[t, t + k]`` -- ``band[0]`` is the posterior variance
+    of the generated trajectory --, zero where ``t + k`` is at or past the utterance's length; ``logdet`` ``(B, static_dim)``.
+    ``band=False``: the factorisation alone, ``(None, logdet)``.  ``out``: a float64 CUDA tensor for the band.  A system that is
+    not positive definite raises ``numpy.linalg.LinAlgError`` naming the first failing (utterance, dim, frame), as ``mlpg`` does.
+    Window extents of at most 1."""
+    from .. import _trajectory_calls as TH
+    torch = _hip.torch_mod()
+    nw = _hip._nw(windows)
+    is_np = not torch.is_tensor(variances)
+    v = None
+    if variances is None:
+        dev = _hip.require_gpu(out.device if out is not None else None)
+        D, dtype = nw, torch.float64
+    else:
+        v, _ = _as_device_batch(variances)
+        v = v.contiguous() if v.dim() != 3 else v
+        dev, D, dtype = v.device, v.shape[-1], v.dtype
+        if v.dim() not in (1, 3):
+            raise ValueError("variances must be (B, Tmax, D), (D,) or None, got %s" % (tuple(v.shape),))
+    if nw < 1 or D % nw:
+        raise ValueError("D = %d is not a multiple of the %d windows" % (D, nw))
+    if v is not None and v.dim() == 3:
+        if (B is not None and B != v.shape[0]) or (Tmax is not None and Tmax != v.shape[1]):
+            raise ValueError("B and Tmax disagree with the variances' shape %s" % (tuple(v.shape),))
+        B, Tmax = v.shape[:2]
+    else:
+        host_len = None if lengths is None else np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths).reshape(-1)
+        B = int(B) if B is not None else (len(host_len) if host_len is not None else 1)
+        if Tmax is None:
+            if host_len is None:
+                raise ValueError("global or unit variances need Tmax or lengths")
+            Tmax = int(host_len.max()) if len(host_len) else 0
+    L = _device_lengths(lengths, dev)
+    bnd, logdet, status = TH.covariance(v, windows, L, int(B), int(Tmax), D, dtype=dtype, device=dev, want_band=bool(band), band=out)
+    raise_on_trajectory_status(status)
+    if is_np and out is None:
+        return (bnd.cpu().numpy() if bnd is not None else None), logdet.cpu().numpy()
+    return bnd, logdet
+
+
+def mlpg_variance(variance_frames, windows):
+    """The posterior variance of the trajectory ``mlpg(mean_frames, variance_frames, windows)`` generates, ``(T, D) -> (T,
+    static_dim)`` float64: ``diag(R^-1)`` (the reference has it for unit variances alone, as a dense ``T x T`` inverse).
+    ``variance_frames``: ``(T, D)`` numpy, float32 or float64."""
+    v = _as_float(variance_frames)
+    assert v.ndim == 2
+    band, _ = mlpg_covariance_batch(v[None], windows)
+    return band[0, 0]
+
+
+def mlpg_logdet(variance_frames, windows):
+    """``log det R`` of the trajectory distribution per static dim, ``(T, D) -> (static_dim,)`` float64."""
+    v = _as_float(variance_frames)
+    assert v.ndim == 2
+    return mlpg_covariance_batch(v[None], windows, band=False)[1][0]
 
 
 # registry of MLPG matrices handed out by unit_variance_mlpg_matrix, so that

@@ -73,6 +73,11 @@
         nnmk_joint_write together and apart, the LIVE keep rule, the same rows composed from delta_features and torch operations,
         torch's plain copy of the rows the write stage stores, and the reference-style per-utterance host loop (scaled); protocol
         as f0; also written to profiles/joint.json (NNMNKWII_JOINT_PROFILE names another file)
+  trajcov : (only with --only trajcov) the trajectory covariance (nnmk_traj_covariance: band of R^-1, log det R) and covariance +
+        likelihood with both gradients (nnmk_traj_nll) at float64 256 x 1000 x 180, lengths in [500, 1000], per-frame variances:
+        each against torch's plain copy of the bytes it must move, and -- at 8 x 500 x 180, where the dense matrices fit -- against
+        the composed route (batched dense torch.linalg.inv / logdet, and autograd of the dense likelihood); protocol as f0; also
+        written to profiles/trajcov.json (NNMNKWII_TRAJCOV_PROFILE names another file)
 
 Each line carries the GPU time (HIP events on the launch stream), the algorithmic bytes, GB/s, and a
 bounded CPU baseline from the oracle on the same host (the checker, timed like bench.py's cpu_baseline).
@@ -1133,6 +1138,152 @@ def _run(only, quick, device_index):
         emit(**res)
         if not args.quick:
             out_path = os.environ.get("NNMNKWII_GVMLPG_PROFILE") or os.path.join(ROOT, "profiles", "gvmlpg.json")
+            with open(out_path, "w") as fh:
+                json.dump(res, fh, indent=1, sort_keys=True)
+                fh.write("\n")
+
+    # ---- trajcov: the band of the trajectory covariance, log det R, the likelihood and its gradients; only with --only trajcov ----
+    if args.only and "trajcov" in args.only.split(","):
+        from nnmnkwii_amd import _trajectory_calls as TC
+        nw, Q = len(WINDOWS), 2
+        res = dict(path="trajcov", hbm_peak_gbs=HBM_PEAK_GBS, dtype="float64", windows="static + delta + delta-delta")
+
+        def timed(fn, steps, warmup=2):
+            gpu_time(fn, steps=1, warmup=warmup)                                  # warm-up and settled clocks
+            return spread(events(fn, steps))
+
+        def case(B, T, sd, lo):
+            rng = np.random.RandomState(1234)
+            lens = rng.randint(lo, T + 1, size=B).astype(np.int32)
+            g2 = torch.Generator(device=dev).manual_seed(4321)
+            m = torch.randn(B, T, nw * sd, dtype=torch.float64, device=dev, generator=g2)
+            v = torch.rand(B, T, nw * sd, dtype=torch.float64, device=dev, generator=g2) + 0.5
+            c = torch.randn(B, T, sd, dtype=torch.float64, device=dev, generator=g2)
+            return lens, torch.from_numpy(lens).to(dev), m, v, c
+
+        def device_route(B, T, sd, L, m, v, c, steps):
+            D = nw * sd
+            band = torch.empty((Q + 1, B, T, sd), dtype=torch.float64, device=dev)
+            logdet = torch.empty((B, sd), dtype=torch.float64, device=dev)
+            status = torch.empty((B, sd), dtype=torch.int32, device=dev)
+            cbar, _ = _hip.forward(m, v, WINDOWS, L, want_status=False)
+            cov = lambda: TC.covariance(v, WINDOWS, L, B, T, D, band=band, logdet=logdet, status=status)  # noqa: E731
+            fwd = lambda: TC.covariance(v, WINDOWS, L, B, T, D, want_band=False, logdet=logdet, status=status)  # noqa: E731
+
+            def both():
+                cov()
+                return TC.nll(m, v, WINDOWS, cbar, c, L, band, logdet)
+            r = dict(cov_ms=timed(cov, steps))
+            r["logdet_only_ms"] = timed(fwd, steps)
+            r["cov_nll_grads_ms"] = timed(both, steps)
+            nll, gm, gv = both()
+            torch.cuda.synchronize()
+            return r, band, logdet, status, nll, gm, gv
+
+        # -- the full shape: against a plain copy of the bytes each must move
+        B, T, sd = (16, 200, 60) if args.quick else (256, 1000, 60)
+        D = nw * sd
+        lens, L, m, v, c = case(B, T, sd, T // 2)
+        live = int(lens.sum())
+        r, band, logdet, status, nll, gm, gv = device_route(B, T, sd, L, m, v, c, 20)
+        cov_bytes = 8.0 * (live * D + (Q + 1) * B * T * sd)                     # the variances in, every row of the band out
+        nll_bytes = 8.0 * (2 * live * D + 2 * live * sd + (Q + 1) * live * sd + 2 * B * T * D)   # means, variances, cbar, target, band in; two gradients out
+        for key, nbytes in (("cov", cov_bytes), ("cov_nll_grads", cov_bytes + nll_bytes)):
+            src = torch.empty(int(nbytes // 16), dtype=torch.float64, device=dev)
+            dst = torch.empty_like(src)
+            copy_ms = timed(lambda: dst.copy_(src), 20)
+            ms = r["%s_ms" % key]["median_ms"]
+            r["%s_bytes" % key] = nbytes
+            r["%s_copy_ms" % key] = copy_ms
+            r["%s_hbm_frac" % key] = nbytes / (ms * 1e6) / HBM_PEAK_GBS
+            r["%s_over_copy" % key] = ms / copy_ms["median_ms"]
+            del src, dst
+        r.update(B=B, T=T, D=D, live_frames=live, bad_systems=int((status != 0).sum()), wavefronts=B * ((sd + 63) // 64))
+        res["full"] = r
+        del m, v, c, band, gm, gv
+
+        # -- a shape whose dense matrices fit: against the composed route
+        B, T, sd = (2, 100, 60) if args.quick else (8, 500, 60)
+        D = nw * sd
+        lens, L, m, v, c = case(B, T, sd, T)                                     # full lengths: the dense route has no padding rule
+        r, band, logdet, status, nll, gm, gv = device_route(B, T, sd, L, m, v, c, 20)
+        W = torch.zeros((nw, T, T), dtype=torch.float64, device=dev)
+        for w, (l, u, cf) in enumerate(WINDOWS):
+            for k in range(-l, u + 1):
+                i = torch.arange(max(0, -k), min(T, T - k), device=dev)
+                W[w, i, i + k] = float(cf[l + k])
+        edge = torch.ones((nw, T), dtype=torch.float64, device=dev)
+        edge[1:, 0] = 0.0
+        edge[1:, T - 1] = 0.0
+
+        def dense_R(var):
+            tau = (1.0 / var).view(B, T, nw, sd).permute(0, 3, 2, 1) * edge       # (B, sd, nw, T)
+            return torch.einsum("wts,bdwt,wtu->bdsu", W, tau, W), tau
+
+        lu = dict(chunk=B * sd)     # systems per call of torch.linalg.inv / solve / logdet: all of them, an utterance's, or one
+
+        def chunked(fn, *ts):
+            n = ts[0].shape[0]
+            outs = [fn(*[t[k:k + lu["chunk"]] for t in ts]) for k in range(0, n, lu["chunk"])]
+            return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+        def inv_logdet(R):
+            Rf = R.reshape(B * sd, T, T)
+            return chunked(torch.linalg.inv, Rf).view(B, sd, T, T), chunked(torch.logdet, Rf).view(B, sd)
+
+        def solve_logdet(R, rhs):
+            Rf = R.reshape(B * sd, T, T)
+            return chunked(torch.linalg.solve, Rf, rhs.reshape(B * sd, T)).view(B, sd, T), chunked(torch.logdet, Rf).view(B, sd)
+
+        def composed_cov():
+            R, _ = dense_R(v)
+            return inv_logdet(R)
+
+        def composed_nll():
+            mm, vv = m.detach().requires_grad_(), v.detach().requires_grad_()
+            R, tau = dense_R(vv)
+            mu = mm.view(B, T, nw, sd).permute(0, 3, 2, 1)                         # (B, sd, nw, T)
+            rhs = torch.einsum("wts,bdwt->bds", W, tau * mu)
+            cb_, ld_ = solve_logdet(R, rhs)
+            e = c.permute(0, 2, 1) - cb_
+            out = 0.5 * torch.einsum("bds,bdsu,bdu->bd", e, R, e) - 0.5 * ld_ + 0.5 * T * math.log(2 * math.pi)
+            out.sum().backward()
+            return out.detach(), mm.grad, vv.grad
+        for chunk in (B * sd, sd, 1):     # the BLAS library's batched LU and triangular solves can run out of their own workspace
+            lu["chunk"] = chunk
+            try:
+                composed_cov()
+                composed_nll()
+                torch.cuda.synchronize()
+                break
+            except RuntimeError as err:
+                r["composed_error_at_%d_systems_a_call" % chunk] = str(err).splitlines()[0][:200]
+        r["composed_systems_per_call"] = lu["chunk"]
+        r["composed_cov_ms"] = timed(composed_cov, 5, warmup=1)
+        r["composed_nll_grads_ms"] = timed(composed_nll, 5, warmup=1)
+        S, ld = composed_cov()
+        cn, cgm, cgv = composed_nll()
+        r["band_max_abs_diff_vs_composed"] = float(max((torch.diagonal(S, k, 2, 3).permute(0, 2, 1) - band[k, :, :T - k]).abs().max() for k in range(Q + 1)))
+        r["logdet_max_abs_diff_vs_composed"] = float((ld - logdet).abs().max())
+        r["nll_max_rel_diff_vs_composed"] = float(((cn - nll).abs() / cn.abs()).max())
+        r["grad_means_max_abs_diff_vs_composed"] = float((cgm - gm).abs().max())
+        r["grad_vars_max_abs_diff_vs_composed"] = float((cgv - gv).abs().max())
+        r["composed_cov_over_cov"] = r["composed_cov_ms"]["median_ms"] / r["cov_ms"]["median_ms"]
+        r["composed_nll_over_cov_nll"] = r["composed_nll_grads_ms"]["median_ms"] / r["cov_nll_grads_ms"]["median_ms"]
+        r.update(B=B, T=T, D=D, dense_bytes_per_matrix=8.0 * B * sd * T * T)
+        res["dense_fits"] = r
+        res["note"] = ("HIP-event times of single calls on settled clocks (median, min, max, quartiles of 20; 5 for the composed routes).  "
+                       "cov: ONE launch of nnmk_traj_covariance into a caller's band; logdet_only: the same with want_band = 0; cov_nll_grads: "
+                       "that launch plus ONE of nnmk_traj_nll with both gradients (cbar is made beforehand by mlpg_hip_forward and not timed).  "
+                       "bytes: the variances of the live frames in and every row of the band out; for the likelihood also means, variances, cbar, "
+                       "target and band of the live frames in and two full gradients out.  copy: torch's dst.copy_(src) of half those bytes (it "
+                       "reads and writes them).  hbm_frac: bytes over time as a fraction of 8 TB/s.  composed: R assembled densely by einsum, "
+                       "then inverse and log-determinant over all (B, sd) systems, and autograd of the dense likelihood through a dense "
+                       "solve and log-determinant: torch.linalg.inv / solve / logdet over composed_systems_per_call systems a call (all of "
+                       "them where the library's batched routines take that); full lengths.  No counters were collected; no time is asserted anywhere")
+        emit(**res)
+        if not args.quick:
+            out_path = os.environ.get("NNMNKWII_TRAJCOV_PROFILE") or os.path.join(ROOT, "profiles", "trajcov.json")
             with open(out_path, "w") as fh:
                 json.dump(res, fh, indent=1, sort_keys=True)
                 fh.write("\n")
