@@ -7,12 +7,12 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["capi.hip", "streams_api.hip", "host_api.hip", "mlpg_generic.hip", "mlpg_wave.hip", "mlpg_wave_fwd_f64.hip", "mlpg_wave_fwd_f32.hip",
            "mlpg_wave_bwd_f64.hip", "mlpg_wave_bwd_f32.hip", "mlpg_wave_fused.hip", "mlpg_strip.hip", "mlpg_strip_fwd_f64.hip",
-           "mlpg_strip_fwd_f32.hip", "mlpg_strip_bwd_f64.hip", "mlpg_strip_bwd_f32.hip", "mlpg_strip_std_fwd_f64.hip", "mlpg_strip_std_fwd_f32.hip", "mlpg_strip_std_bwd_f64.hip", "mlpg_strip_std_bwd_f32.hip", "mlpg_strip_multi_f64.hip", "mlpg_strip_multi_f32.hip", "mlpg_const.hip", "mlpg_const_fwd_f64.hip", "mlpg_const_fwd_f32.hip", "mlpg_const_bwd_f64.hip", "mlpg_const_bwd_f32.hip", "mlpg_const_multi_f64.hip", "mlpg_const_multi_f32.hip", "mlpg_chunk.hip", "mlpg_chunk_fwd_f64.hip", "mlpg_chunk_fwd_f32.hip", "mlpg_chunk_bwd_f64.hip", "mlpg_chunk_bwd_f32.hip", "mlpg_fir.hip", "mlpg_vargrad.hip", "mlpg_streams_bwd.hip", "dtw.hip", "dtw_fast.hip", "dtw_costs.hip", "modspec.hip", "modspec_chirp.hip", "modspec_filter.hip", "modspec_dft.hip", "modspec_api.hip", "gmm_em.hip", "kmeans.hip", "postfilter.hip", "gmm_traj.hip", "mlpg_gv.hip", "colstats.hip", "frame_metrics.hip", "frame_expand.hip", "f0_interp.hip", "wave_codec.hip", "joint_rows.hip", "frame_keep.hip", "mlpg_trajcov.hip"]
+           "mlpg_strip_fwd_f32.hip", "mlpg_strip_bwd_f64.hip", "mlpg_strip_bwd_f32.hip", "mlpg_strip_std_fwd_f64.hip", "mlpg_strip_std_fwd_f32.hip", "mlpg_strip_std_bwd_f64.hip", "mlpg_strip_std_bwd_f32.hip", "mlpg_strip_multi_f64.hip", "mlpg_strip_multi_f32.hip", "mlpg_const.hip", "mlpg_const_fwd_f64.hip", "mlpg_const_fwd_f32.hip", "mlpg_const_bwd_f64.hip", "mlpg_const_bwd_f32.hip", "mlpg_const_multi_f64.hip", "mlpg_const_multi_f32.hip", "mlpg_chunk.hip", "mlpg_chunk_fwd_f64.hip", "mlpg_chunk_fwd_f32.hip", "mlpg_chunk_bwd_f64.hip", "mlpg_chunk_bwd_f32.hip", "mlpg_fir.hip", "mlpg_vargrad.hip", "mlpg_streams_bwd.hip", "dtw.hip", "dtw_fast.hip", "dtw_costs.hip", "modspec.hip", "modspec_chirp.hip", "modspec_filter.hip", "modspec_dft.hip", "modspec_api.hip", "gmm_em.hip", "kmeans.hip", "postfilter.hip", "gmm_traj.hip", "mlpg_gv.hip", "colstats.hip", "frame_metrics.hip", "frame_expand.hip", "f0_interp.hip", "wave_codec.hip", "joint_rows.hip", "frame_keep.hip", "mlpg_trajcov.hip", "mlpg_trajsample.hip"]
 HEADERS = ["common.h", "device_prims.h", "mlpg_strip_geom.h", "assemble.h", "vargrad_element.h", "mlpg_wave_impl.h", "mlpg_strip_impl.h", "mlpg_const_impl.h", "mlpg_chunk_impl.h", "modspec_fft.h", "postfilter_table.h", os.path.join("..", "..", "include", "mlpg_hip.h"),
            os.path.join("..", "..", "include", "nnmnkwii_metrics.h"), os.path.join("..", "..", "include", "nnmnkwii_frontend.h"),
            os.path.join("..", "..", "include", "nnmnkwii_f0.h"), os.path.join("..", "..", "include", "nnmnkwii_wave.h"),
            os.path.join("..", "..", "include", "nnmnkwii_joint.h"), os.path.join("..", "..", "include", "nnmnkwii_silence.h"),
-           os.path.join("..", "..", "include", "nnmnkwii_trajectory.h")]
+           os.path.join("..", "..", "include", "nnmnkwii_trajectory.h"), os.path.join("..", "..", "include", "nnmnkwii_sample.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 # The DTW kernels must round exactly like the CPU oracle (separate multiply and add); the MLPG
 # kernels are free to fuse multiply-adds.
@@ -24,7 +24,8 @@ FILE_FLAGS = {"mlpg_fir.hip": ["-ffp-contract=fast", "-mllvm", "-pragma-unroll-t
                  for d in ("fwd", "bwd") for t in ("f64", "f32")},
               "dtw_fast.hip": ["-ffp-contract=off"], "dtw.hip": ["-ffp-contract=off"], "dtw_costs.hip": ["-ffp-contract=off"], "modspec.hip": ["-ffp-contract=off"], "modspec_chirp.hip": ["-ffp-contract=off"], "modspec_filter.hip": ["-ffp-contract=off"], "modspec_dft.hip": ["-ffp-contract=off"], "gmm_em.hip": ["-ffp-contract=off"], "kmeans.hip": ["-ffp-contract=off"], "postfilter.hip": ["-ffp-contract=off"], "gmm_traj.hip": ["-ffp-contract=off"], "mlpg_gv.hip": ["-ffp-contract=off"], "colstats.hip": ["-ffp-contract=off"], "frame_metrics.hip": ["-ffp-contract=off"], "frame_expand.hip": ["-ffp-contract=off"], "f0_interp.hip": ["-ffp-contract=off"],
               "wave_codec.hip": ["-ffp-contract=off"], "joint_rows.hip": ["-ffp-contract=off"],
-              "frame_keep.hip": ["-ffp-contract=off"], "mlpg_trajcov.hip": ["-ffp-contract=off"]}
+              "frame_keep.hip": ["-ffp-contract=off"], "mlpg_trajcov.hip": ["-ffp-contract=off"],
+              "mlpg_trajsample.hip": ["-ffp-contract=off"]}
 COST = {"mlpg_wave_bwd_f64.hip": 29, "mlpg_wave_bwd_f32.hip": 27, "mlpg_chunk_bwd_f64.hip": 26, "mlpg_chunk_bwd_f32.hip": 26, "mlpg_strip_bwd_f64.hip": 23,
         "mlpg_strip_bwd_f32.hip": 23, "mlpg_chunk_fwd_f64.hip": 20, "mlpg_chunk_fwd_f32.hip": 20, "mlpg_fir.hip": 18, "mlpg_wave_fwd_f64.hip": 18,
         "mlpg_wave_fwd_f32.hip": 15, "mlpg_generic.hip": 14, "mlpg_strip_fwd_f32.hip": 13, "mlpg_strip_fwd_f64.hip": 12, "mlpg_const_bwd_f32.hip": 12,
@@ -52,7 +53,7 @@ def _headers_of(src):
     hs = [h for h in HEADERS if h not in ("mlpg_wave_impl.h", "mlpg_strip_impl.h", "mlpg_const_impl.h", "mlpg_chunk_impl.h", "modspec_fft.h", "postfilter_table.h")
           and not h.endswith("nnmnkwii_metrics.h") and not h.endswith("nnmnkwii_frontend.h") and not h.endswith("nnmnkwii_f0.h")
           and not h.endswith("nnmnkwii_wave.h") and not h.endswith("nnmnkwii_joint.h") and not h.endswith("nnmnkwii_silence.h")
-          and not h.endswith("nnmnkwii_trajectory.h")]
+          and not h.endswith("nnmnkwii_trajectory.h") and not h.endswith("nnmnkwii_sample.h")]
     if src == "frame_metrics.hip":
         hs.append(os.path.join("..", "..", "include", "nnmnkwii_metrics.h"))
     if src == "frame_expand.hip":
@@ -67,6 +68,8 @@ def _headers_of(src):
         hs += [os.path.join("..", "..", "include", "nnmnkwii_silence.h"), os.path.join("..", "..", "include", "nnmnkwii_frontend.h")]
     if src == "mlpg_trajcov.hip":
         hs.append(os.path.join("..", "..", "include", "nnmnkwii_trajectory.h"))
+    if src == "mlpg_trajsample.hip":
+        hs.append(os.path.join("..", "..", "include", "nnmnkwii_sample.h"))
     if src == "postfilter.hip":
         hs.append("postfilter_table.h")
     if src in ("modspec.hip", "modspec_chirp.hip", "modspec_filter.hip"):

@@ -26,6 +26,9 @@ __all__ = [
     "mlpg_covariance_batch",
     "mlpg_variance",
     "mlpg_logdet",
+    "mlpg_sample_batch",
+    "mlpg_sample",
+    "mlpg_whiten_batch",
 ]
 
 
@@ -518,6 +521,107 @@ def mlpg_logdet(variance_frames, windows):
     v = _as_float(variance_frames)
     assert v.ndim == 2
     return mlpg_covariance_batch(v[None], windows, band=False)[1][0]
+
+
+# ---- draws from the trajectory distribution N(c; cbar, R^-1) and the whitening map ----------------------------------
+def _trajectory_factor(means, variances, windows, lengths):
+    """(means on the device, variances or None, lengths or None, factor, logdet, status, was numpy, the means' dtype) for the
+    functions below; the means and variances brought to one dtype as mlpg_batch does."""
+    from .. import _sample_calls as SC
+    torch = _hip.torch_mod()
+    m, is_np = _as_device_batch(means)
+    m = m.detach()
+    if m.dim() != 3:
+        raise ValueError("means must be (B, Tmax, D), got %s" % (tuple(m.shape),))
+    B, Tmax, D = m.shape
+    out_dtype = m.dtype
+    v = None
+    if variances is not None:
+        v = _as_device_batch(variances, m.device)[0].detach()
+        if v.dim() not in (1, 3) or (v.dim() == 3 and v.shape != m.shape) or (v.dim() == 1 and v.shape[0] != D):
+            raise ValueError("variances must be like the means, (D,) or None, got %s" % (tuple(v.shape),))
+        m, v = _match_dtypes(m, v)
+        v = v.contiguous() if v.dim() == 1 else v
+    L = _device_lengths(lengths, m.device)
+    fac, logdet, status = SC.factor(v, windows, L, B, Tmax, D, dtype=m.dtype, device=m.device)
+    raise_on_trajectory_status(status)
+    return m, v, L, fac, logdet, status, is_np, out_dtype
+
+
+def mlpg_sample_batch(means, variances, windows, lengths=None, num_samples=1, *, noise=None, generator=None, cbar=None, return_logdet=False,
+                      out=None):
+    """Draws from MLPG's trajectory distribution ``N(c; cbar, R^-1)`` over a zero-padded batch: ``c = cbar + L^-T D^-1/2 z`` with
+    ``R = L D L'`` the banded factor ``mlpg_covariance_batch`` eliminates with and ``z`` white.  Two launches (``nnmk_draw_factor``,
+    ``nnmk_draw_sample``) after the mean's: ``O(T Q)`` per draw, no dense ``T x T`` factor anywhere.
+
+    ``means`` ``(B, Tmax, D)`` and ``variances`` (like the means, a global ``(D,)`` or ``None``): numpy arrays or CUDA tensors,
+    float32 or float64.  ``cbar`` ``(B, Tmax, static_dim)``: the mean trajectory, if it is at hand; otherwise ``mlpg_batch(means,
+    variances, windows, lengths)`` gives it.  ``noise`` ``(num_samples, B, Tmax, static_dim)``: the white ``z``; otherwise
+    ``torch.randn(..., generator=generator)`` on the device (``generator``: a CUDA ``torch.Generator``, for reproducible draws).
+    Returns ``(num_samples, B, Tmax, static_dim)`` in the dtype of the means -- zero at or past an utterance's length --, numpy for
+    numpy means, else a CUDA tensor (``out``, if given); with ``return_logdet`` also ``log det R`` ``(B, static_dim)`` float64.  All
+    work goes on the current stream.  The draws are NOT differentiable: tensors that require a gradient are accepted and the result is
+    detached.  A system that is not positive definite raises ``numpy.linalg.LinAlgError`` naming utterance, dim and frame.
+    Window extents of at most 1."""
+    from .. import _sample_calls as SC
+    torch = _hip.torch_mod()
+    K = int(num_samples)
+    if K < 0:
+        raise ValueError("num_samples must not be negative, got %d" % K)
+    nw = _hip._nw(windows)
+    if nw < 1 or np.shape(means)[-1] % nw:
+        raise ValueError("D = %d is not a multiple of the %d windows" % (np.shape(means)[-1], nw))
+    if noise is not None and (np.ndim(noise) != 4 or np.shape(noise)[0] != K):
+        raise ValueError("noise must be (num_samples = %d, B, Tmax, static_dim), got %s" % (K, tuple(np.shape(noise))))
+    m, v, L, fac, logdet, status, is_np, out_dtype = _trajectory_factor(means, variances, windows, lengths)
+    B, Tmax, D = m.shape
+    sd = D // nw
+    if cbar is None:
+        cb = mlpg_batch(m, v, windows, L)
+    else:
+        cb = _as_device_batch(cbar, m.device)[0].detach()
+    cb = cb.to(m.dtype)
+    if noise is None:
+        z = torch.randn((K, B, Tmax, sd), dtype=m.dtype, device=m.device, generator=generator)
+    else:
+        z = _as_device_batch(noise, m.device)[0].detach().to(m.dtype)
+    x = SC.sample(fac, status, L, z, cb, out=out)
+    if x.dtype != out_dtype and out is None:
+        x = x.to(out_dtype)
+    if is_np and out is None:
+        x, logdet = x.cpu().numpy(), logdet.cpu().numpy()
+    return (x, logdet) if return_logdet else x
+
+
+def mlpg_sample(mean_frames, variance_frames, windows, num_samples=1, *, noise=None, generator=None):
+    """``num_samples`` draws from the trajectory distribution of one utterance, ``(T, D) -> (num_samples, T, static_dim)`` in the
+    dtype of ``mean_frames``; ``mlpg(mean_frames, variance_frames, windows)`` is their mean.  ``variance_frames``: ``(T, D)`` or a
+    global ``(D,)``; ``noise`` ``(num_samples, T, static_dim)``.  See :func:`mlpg_sample_batch`."""
+    mean_frames = np.asarray(mean_frames)
+    variance_frames = np.asarray(variance_frames)
+    T, D = mean_frames.shape
+    if not (variance_frames.ndim == 1 and variance_frames.shape[0] == D):
+        assert mean_frames.shape == variance_frames.shape
+        variance_frames = variance_frames[None]
+    x = mlpg_sample_batch(mean_frames[None], variance_frames, windows, None, num_samples, noise=None if noise is None else np.asarray(noise)[:, None],
+                          generator=generator)
+    return x[:, 0].astype(mean_frames.dtype, copy=False)
+
+
+def mlpg_whiten_batch(x, means, variances, windows, lengths=None, *, cbar=None):
+    """The inverse of :func:`mlpg_sample_batch`: ``z = D^1/2 L' (x - cbar)``, the trajectories ``x`` ``(K, B, Tmax, static_dim)`` (or
+    ``(B, Tmax, static_dim)``: one per utterance) whitened under the model.  ``1/2 sum_t z^2`` is the quadratic term of the
+    trajectory likelihood.  Arguments and result as :func:`mlpg_sample_batch`; not differentiable either."""
+    from .. import _sample_calls as SC
+    m, v, L, fac, _, status, is_np, out_dtype = _trajectory_factor(means, variances, windows, lengths)
+    xs = _as_device_batch(x, m.device)[0].detach().to(m.dtype)
+    one = xs.dim() == 3
+    if one:
+        xs = xs[None]
+    cb = mlpg_batch(m, v, windows, L) if cbar is None else _as_device_batch(cbar, m.device)[0].detach()
+    z = SC.whiten(fac, status, L, xs, cb.to(m.dtype))
+    z = (z[0] if one else z).to(out_dtype)
+    return z.cpu().numpy() if is_np else z
 
 
 # registry of MLPG matrices handed out by unit_variance_mlpg_matrix, so that

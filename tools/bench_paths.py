@@ -78,6 +78,11 @@
         each against torch's plain copy of the bytes it must move, and -- at 8 x 500 x 180, where the dense matrices fit -- against
         the composed route (batched dense torch.linalg.inv / logdet, and autograd of the dense likelihood); protocol as f0; also
         written to profiles/trajcov.json (NNMNKWII_TRAJCOV_PROFILE names another file)
+  trajsample : (only with --only trajsample) draws from the trajectory distribution at the same shape: nnmk_draw_factor (against
+        nnmk_traj_covariance's forward sweep), nnmk_draw_sample at K = 1, kDrawGroup and 16, nnmk_draw_whiten at K = 1, each against
+        torch's plain copy of the bytes it must move, and -- at 8 x 500 x 180 -- against the composed route (dense R, torch's Cholesky
+        factor, a triangular solve); protocol as f0; also written to profiles/trajsample.json (NNMNKWII_TRAJSAMPLE_PROFILE names
+        another file)
 
 Each line carries the GPU time (HIP events on the launch stream), the algorithmic bytes, GB/s, and a
 bounded CPU baseline from the oracle on the same host (the checker, timed like bench.py's cpu_baseline).
@@ -1284,6 +1289,122 @@ def _run(only, quick, device_index):
         emit(**res)
         if not args.quick:
             out_path = os.environ.get("NNMNKWII_TRAJCOV_PROFILE") or os.path.join(ROOT, "profiles", "trajcov.json")
+            with open(out_path, "w") as fh:
+                json.dump(res, fh, indent=1, sort_keys=True)
+                fh.write("\n")
+
+    # ---- trajsample: draws from the trajectory distribution and the whitening map; only with --only trajsample ----
+    if args.only and "trajsample" in args.only.split(","):
+        from nnmnkwii_amd import _sample_calls as SC, _trajectory_calls as TC
+        nw, Q, G = len(WINDOWS), 2, SC.draw_group()
+        res = dict(path="trajsample", hbm_peak_gbs=HBM_PEAK_GBS, dtype="float64", windows="static + delta + delta-delta", draw_group=G)
+
+        def timed(fn, steps, warmup=2):
+            gpu_time(fn, steps=1, warmup=warmup)                                  # warm-up and settled clocks
+            return spread(events(fn, steps))
+
+        def case(B, T, sd, lo, K):
+            rng = np.random.RandomState(1234)
+            lens = rng.randint(lo, T + 1, size=B).astype(np.int32)
+            g2 = torch.Generator(device=dev).manual_seed(4321)
+            v = torch.rand(B, T, nw * sd, dtype=torch.float64, device=dev, generator=g2) + 0.5
+            c = torch.randn(B, T, sd, dtype=torch.float64, device=dev, generator=g2)
+            z = torch.randn(K, B, T, sd, dtype=torch.float64, device=dev, generator=g2)
+            return lens, torch.from_numpy(lens).to(dev), v, c, z
+
+        def against_copy(r, key, nbytes):
+            src = torch.empty(int(nbytes // 16), dtype=torch.float64, device=dev)
+            dst = torch.empty_like(src)
+            copy_ms = timed(lambda: dst.copy_(src), 20)
+            ms = r["%s_ms" % key]["median_ms"]
+            r["%s_bytes" % key] = nbytes
+            r["%s_copy_ms" % key] = copy_ms
+            r["%s_hbm_frac" % key] = nbytes / (ms * 1e6) / HBM_PEAK_GBS
+            r["%s_over_copy" % key] = ms / copy_ms["median_ms"]
+
+        # -- the full shape: against a plain copy of the bytes each must move
+        B, T, sd = (16, 200, 60) if args.quick else (256, 1000, 60)
+        D = nw * sd
+        KS = sorted({1, G, 16})
+        lens, L, v, c, z = case(B, T, sd, T // 2, max(KS))
+        live = int(lens.sum())
+        fac = torch.empty((Q + 1, B, T, sd), dtype=torch.float64, device=dev)
+        logdet = torch.empty((B, sd), dtype=torch.float64, device=dev)
+        status = torch.empty((B, sd), dtype=torch.int32, device=dev)
+        out = torch.empty_like(z)
+        r = dict(factor_ms=timed(lambda: SC.factor(v, WINDOWS, L, B, T, D, factor=fac, logdet=logdet, status=status), 20))
+        r["traj_covariance_want_band_0_ms"] = timed(lambda: TC.covariance(v, WINDOWS, L, B, T, D, want_band=False, logdet=logdet, status=status), 20)
+        r["factor_over_traj_covariance_want_band_0"] = r["factor_ms"]["median_ms"] / r["traj_covariance_want_band_0_ms"]["median_ms"]
+        against_copy(r, "factor", 8.0 * (live * D + (Q + 1) * B * T * sd))         # the variances in, every row of the factor out
+        SC.factor(v, WINDOWS, L, B, T, D, factor=fac, logdet=logdet, status=status)
+        for K in KS:
+            key = "sample_K%d" % K
+            r[key + "_ms"] = timed(lambda: SC.sample(fac, status, L, z[:K], c, out=out[:K]), 20)
+            r[key + "_per_draw_ms"] = r[key + "_ms"]["median_ms"] / K
+            against_copy(r, key, 8.0 * ((Q + 1) * live * sd + K * live * sd + live * sd + K * B * T * sd))   # factor, noise, mean in; K draws out
+        r["per_draw_K%d_over_K1" % G] = r["sample_K%d_per_draw_ms" % G] / r["sample_K1_per_draw_ms"]
+        r["per_draw_K16_over_K1"] = r["sample_K16_per_draw_ms"] / r["sample_K1_per_draw_ms"]
+        back = torch.empty_like(z[:1])
+        r["whiten_K1_ms"] = timed(lambda: SC.whiten(fac, status, L, out[:1], c, out=back), 20)
+        against_copy(r, "whiten_K1", 8.0 * ((Q + 1) * live * sd + live * sd + live * sd + B * T * sd))
+        SC.sample(fac, status, L, z[:1], c, out=out[:1])
+        SC.whiten(fac, status, L, out[:1], c, out=back)
+        torch.cuda.synchronize()
+        mask = (torch.arange(T, device=dev)[None, :] < L[:, None])[None, :, :, None]
+        r["round_trip_max_abs_diff"] = float(((back - z[:1]) * mask).abs().max())
+        r.update(B=B, T=T, D=D, live_frames=live, bad_systems=int((status != 0).sum()), wavefronts=B * ((sd + 63) // 64))
+        res["full"] = r
+        del v, c, z, out, fac, back
+
+        # -- a shape whose dense matrices fit: against the composed route (R by einsum, Cholesky, a triangular solve)
+        B, T, sd = (2, 100, 60) if args.quick else (8, 500, 60)
+        D = nw * sd
+        K = 1
+        lens, L, v, c, z = case(B, T, sd, T, K)                                    # full lengths: the dense route has no padding rule
+        fac, logdet, status = SC.factor(v, WINDOWS, L, B, T, D)
+        out = torch.empty_like(z)
+
+        def device_route():
+            SC.factor(v, WINDOWS, L, B, T, D, factor=fac, logdet=logdet, status=status)
+            return SC.sample(fac, status, L, z, c, out=out)
+        r = dict(factor_sample_ms=timed(device_route, 20))
+        W = torch.zeros((nw, T, T), dtype=torch.float64, device=dev)
+        for w, (l, u, cf) in enumerate(WINDOWS):
+            for k in range(-l, u + 1):
+                i = torch.arange(max(0, -k), min(T, T - k), device=dev)
+                W[w, i, i + k] = float(cf[l + k])
+        edge = torch.ones((nw, T), dtype=torch.float64, device=dev)
+        edge[1:, 0] = 0.0
+        edge[1:, T - 1] = 0.0
+
+        def composed():
+            tau = (1.0 / v).view(B, T, nw, sd).permute(0, 3, 2, 1) * edge         # (B, sd, nw, T)
+            R = torch.einsum("wts,bdwt,wtu->bdsu", W, tau, W)
+            C = torch.linalg.cholesky(R)                                          # R = C C^T
+            x = torch.linalg.solve_triangular(C.transpose(-1, -2), z[0].permute(0, 2, 1).unsqueeze(-1), upper=True)
+            return c + x.squeeze(-1).permute(0, 2, 1)
+        try:
+            composed()
+            torch.cuda.synchronize()
+            r["composed_ms"] = timed(composed, 5, warmup=1)
+            r["draw_max_abs_diff_vs_composed"] = float((composed() - device_route()[0]).abs().max())
+            r["composed_over_factor_sample"] = r["composed_ms"]["median_ms"] / r["factor_sample_ms"]["median_ms"]
+        except RuntimeError as err:
+            r["composed_error"] = str(err).splitlines()[0][:200]
+        r.update(B=B, T=T, D=D, K=K, dense_bytes_per_matrix=8.0 * B * sd * T * T)
+        res["dense_fits"] = r
+        res["note"] = ("HIP-event times of single calls on settled clocks (median, min, max, quartiles of 20; 5 for the composed route).  "
+                       "factor: ONE launch of nnmk_draw_factor into a caller's planes; traj_covariance_want_band_0: nnmk_traj_covariance's "
+                       "forward sweep on the same inputs; sample_K*: ONE launch of nnmk_draw_sample for K draws with a mean (draw_group draws "
+                       "side by side in a lane); whiten_K1: ONE launch of nnmk_draw_whiten.  bytes: the variances of the live frames in and "
+                       "every row of the factor out; for the draws the factor, the noise and the mean of the live frames in and every row of "
+                       "the K draws out.  copy: torch's dst.copy_(src) of half those bytes (it reads and writes them).  hbm_frac: bytes over "
+                       "time as a fraction of 8 TB/s.  composed: R assembled densely by einsum, torch.linalg.cholesky and "
+                       "torch.linalg.solve_triangular over all (B, sd) systems, one draw; factor_sample: the two launches that give the same "
+                       "draw; full lengths.  No counters or traces were collected; no time is asserted anywhere")
+        emit(**res)
+        if not args.quick:
+            out_path = os.environ.get("NNMNKWII_TRAJSAMPLE_PROFILE") or os.path.join(ROOT, "profiles", "trajsample.json")
             with open(out_path, "w") as fh:
                 json.dump(res, fh, indent=1, sort_keys=True)
                 fh.write("\n")
